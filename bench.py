@@ -2,19 +2,24 @@
 """Benchmark of the polydet hot path on MI355X (contract: see the task description).
 
   N = 1 (default)  one step = one 2048x1024 image through DLA-34 + DCNv2 -> sigmoid -> fused
-                   NMS/top-k/decode (BASELINE config 2); `value` = inference img/s.  The same
-                   line carries the 1-GPU training point (`train`, with the DCNv2 backward
-                   rooflines), the DCNv2 forward roofline measured with HIP events inside the timed
-                   region (`roofline`: algorithmic bytes against HBM, the north star's figure;
-                   `roofline_mfma`: the same launch's algorithmic flops against the matrix pipe), the
-                   same launch on other offset fields (`roofline_by_offsets`), BASELINE configs 4 and
-                   5 (`other_configs`) and the CPU oracle timed on a bounded sample (`cpu_baseline`).
-                   stdout carries ONE compact line (< 8 KB: `compact_line`); the full tables go to
-                   stderr and gpurun_out/bench_detail.json (`write_detail`).
+                   NMS/top-k/decode (BASELINE config 2); `value` = inference img/s.
   N > 1            one step = one data-parallel training step (BASELINE config 3: DLA-34 + DCNv2,
                    4 images of 2048x1024 per GPU, 16-vertex cartesian head, l1+iou polygon loss,
                    Adam): forward, losses, backward with bucketed RCCL all-reduce, optimizer.
                    `value` = whole-job training img/s, weak scaling.
+
+A plain run does only what the headline needs: set up, `--warmup` untimed steps, `--steps` timed steps, the
+outputs of the last timed step when `--dump-outputs DIR` is given (`dump_outputs`), and ONE JSON line on
+stdout (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, ...).
+
+`--full` adds everything else, as before: HIP-event probe passes and per-launch timers around the dominant
+launch shapes (`roofline`: the DCNv2 forward's algorithmic bytes against HBM, the north star's figure;
+`roofline_mfma`: its algorithmic flops against the matrix pipe; the convolution and heads rooflines), and at
+N = 1 the 1-GPU training point (`train`, with the DCNv2 backward rooflines), the dominant launch on other
+offset fields (`roofline_by_offsets`), the other arithmetic and the golden-error probe, the end-to-end
+detector point, BASELINE configs 4 and 5 (`other_configs`) and the CPU oracle timed on a bounded sample
+(`cpu_baseline`).  stdout still carries ONE compact line (< 8 KB: `compact_line`); the full tables go to
+stderr and to a side file (`write_detail`).
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks
 itself (a child `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
@@ -37,11 +42,16 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 # MIOpen compiles its convolution kernels on first use (minutes on a fresh box).  Keep its
-# compiled-kernel cache inside the repo so it travels with the tree like our own .so.
+# compiled-kernel cache inside the repo so it travels with the tree like our own .so -- when the
+# tree is writable: in a read-only checkout MIOpen keeps its default per-user locations.
 _MIOPEN_CACHE = os.path.join(ROOT, ".miopen_cache")
-os.environ.setdefault("MIOPEN_CUSTOM_CACHE_DIR", _MIOPEN_CACHE)
-os.environ.setdefault("MIOPEN_USER_DB_PATH", os.path.join(_MIOPEN_CACHE, "db"))
-os.makedirs(os.environ["MIOPEN_USER_DB_PATH"], exist_ok=True)
+for _var, _path in (("MIOPEN_CUSTOM_CACHE_DIR", _MIOPEN_CACHE),
+                    ("MIOPEN_USER_DB_PATH", os.path.join(_MIOPEN_CACHE, "db"))):
+    try:
+        os.makedirs(os.environ.get(_var, _path), exist_ok=True)
+    except OSError:
+        continue
+    os.environ.setdefault(_var, _path)
 
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s
 MFMA_F32_PEAK_TF = 157.3       # dense fp32 matrix peak
@@ -82,7 +92,16 @@ def parse(argv=None):
                    help="skip the dominant DCNv2 launch on other offset fields")
     p.add_argument("--no_other_configs", action="store_true",
                    help="skip the BASELINE config 4 / 5 points of the N=1 line")
-    return p.parse_args(argv)
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline (rooflines, training point, other "
+                        "configs and arithmetic, detector point, CPU baseline); the --no_* options trim it")
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                   help="write what the timed step computed in its last step to DIR/<name>.npy (float32, "
+                        "at most 64 MB in all: larger outputs as a fixed, seeded sample)")
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---------------------------------------------------------------- N-rank launch ---
@@ -170,7 +189,8 @@ def build_model(dev, train, dcn_contraction="auto", arch="dla_34", heads=None, o
     return model, sd
 
 
-def timed(fn, steps, warmup, world, tag=""):
+def timed(fn, steps, warmup, world, tag="", keep=None):
+    """Wall time of `steps` calls of fn after `warmup` untimed ones; `keep` receives the last call's result."""
     import torch
     import torch.distributed as dist
     for i in range(warmup):
@@ -181,8 +201,12 @@ def timed(fn, steps, warmup, world, tag=""):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(steps):
-        fn()
+    if keep is None:
+        for _ in range(steps):
+            fn()
+    else:
+        for _ in range(steps):
+            keep["last"] = fn()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -403,9 +427,81 @@ def golden_error(dev):
     return out
 
 
+# ------------------------------------------------------------------ outputs ---
+DUMP_LIMIT = 64 << 20      # bytes of all --dump-outputs files together
+
+
+def infer_outputs(dets, heads):
+    """What a caller of the inference step receives: the decoded detections and the head maps (hm activated)."""
+    out = {"dets": dets}
+    out.update(("head_" + k, v) for k, v in heads.items())
+    return out
+
+
+def train_outputs(result, model):
+    """What a caller of the training step receives (the last stack's head maps, the loss and its terms) and what
+    the step leaves behind (the updated parameters, flattened in registration order)."""
+    import torch
+    output, loss, stats = result
+    out = {"head_" + k: v for k, v in output.items()}
+    out["loss"] = loss
+    out.update(("loss_" + k, v) for k, v in stats.items())
+    with torch.no_grad():
+        out["params"] = torch.cat([p.detach().reshape(-1) for p in model.parameters()])
+    return out
+
+
+def host_arrays(arrays):
+    """Tensors -> host numpy arrays: float64 stays float64, everything else becomes float32."""
+    import numpy as np
+    out = {}
+    for k, v in arrays.items():
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        out[k] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    return out
+
+
+def dump_outputs(arrays, out_dir, limit=DUMP_LIMIT):
+    """Writes out_dir/<name>.npy for every host array, at most `limit` bytes in all: taken smallest first, an array
+    that fits in an even share of the budget left is written whole; the rest (all larger) are each replaced by a
+    fixed, seeded sample of their flattened elements, one share each.  out_dir/manifest.json records the shapes and
+    samples.  Returns the manifest."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    names = sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+    left = limit - 4096 * len(names)                      # room for the .npy headers
+    sampled, share = {}, None
+    for i, k in enumerate(names):
+        if share is None and arrays[k].nbytes > left // (len(names) - i):
+            share = left // (len(names) - i)
+        if share is None:
+            left -= arrays[k].nbytes
+        else:
+            sampled[k] = max(1, share // arrays[k].itemsize)
+    manifest = {}
+    for k in names:
+        a = arrays[k]
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype)}
+        if k in sampled:
+            seed = zlib.crc32(k.encode())
+            idx = np.sort(np.random.default_rng(seed).integers(0, a.size, sampled[k]))
+            a = a.reshape(-1)[idx]
+            entry.update(sample=int(sampled[k]), sample_seed=seed,
+                         sample_rule="flat[np.sort(np.random.default_rng(sample_seed).integers(0, size, sample))]")
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+        manifest[k] = entry
+    with open(os.path.join(out_dir, "manifest.json"), "w") as fh:
+        json.dump(manifest, fh, indent=1, sort_keys=True)
+    return manifest
+
+
 # --------------------------------------------------------------------- legs ---
 def infer_leg(args, dev, world, arch="dla_34", heads=None, rep="cartesian", steps=None, warmup=None,
-              offset_weight_scale=1.0, tag="infer"):
+              offset_weight_scale=1.0, tag="infer", full=True, keep=None):
+    """Times the inference step.  `full`: per-launch HIP-event tables and rooflines beside the timing (returned
+    as the summary; None otherwise).  `keep`: a dict that receives the last timed step's outputs as host arrays
+    (`infer_outputs`)."""
     import torch
     from centerpoly_amd import _C, synth
     from centerpoly_amd.models.decode import polydet_decode
@@ -417,7 +513,7 @@ def infer_leg(args, dev, world, arch="dla_34", heads=None, rep="cartesian", step
         with torch.no_grad():
             out = model(x)[-1]
             hm = out["hm"].sigmoid_()
-            return polydet_decode(hm, out["poly"], out["pseudo_depth"], reg=out["reg"], K=128, rep=rep)
+            return polydet_decode(hm, out["poly"], out["pseudo_depth"], reg=out["reg"], K=128, rep=rep), out
 
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
@@ -425,21 +521,22 @@ def infer_leg(args, dev, world, arch="dla_34", heads=None, rep="cartesian", step
         step()
         torch.cuda.synchronize()
         note("%s warmup %d/%d done" % (tag, i + 1, warmup))
-    # Per-launch HIP events cost a few microseconds of stream time each; around all ~50 DCN / conv3x3 launches of
-    # a step they lengthen it by ~8 %.  So: an untimed probe pass with events on every launch (per-layer table,
-    # and which launch shape dominates each kernel family), then the timed region with events ONLY around the
-    # dominant shape of each family -- those are the durations `roofline` reports.
-    _C.kernel_timer = _C.KernelTimer()
-    probe_steps = 3
-    for _ in range(probe_steps):
-        step()
-    probe = _C.kernel_timer.summary()
-    _C.kernel_timer = None
-    watch = set()
-    for fam in ("dcn_fwd", "conv3x3_fwd", "heads_fused"):
-        keys = [k for k in probe if k[0] == fam]
-        if keys:
-            watch.add(max(keys, key=lambda k: probe[k]["avg_ms"] * probe[k]["launches"]))
+    probe, watch, probe_steps = {}, set(), 0
+    if full:
+        # Per-launch HIP events cost a few microseconds of stream time each; around all ~50 DCN / conv3x3 launches
+        # of a step they lengthen it by ~8 %.  So: an untimed probe pass with events on every launch (per-layer
+        # table, and which launch shape dominates each kernel family), then the timed region with events ONLY
+        # around the dominant shape of each family -- those are the durations `roofline` reports.
+        _C.kernel_timer = _C.KernelTimer()
+        probe_steps = 3
+        for _ in range(probe_steps):
+            step()
+        probe = _C.kernel_timer.summary()
+        _C.kernel_timer = None
+        for fam in ("dcn_fwd", "conv3x3_fwd", "heads_fused"):
+            keys = [k for k in probe if k[0] == fam]
+            if keys:
+                watch.add(max(keys, key=lambda k: probe[k]["avg_ms"] * probe[k]["launches"]))
     run, graphed = step, False
     if args.graph:                                         # opt-in: one HIP graph replay per step
         try:
@@ -448,10 +545,15 @@ def infer_leg(args, dev, world, arch="dla_34", heads=None, rep="cartesian", step
         except Exception as e:                             # noqa: BLE001 -- report and time the eager step
             note("%s: HIP-graph capture failed (%s: %s); timing the eager step" % (tag, type(e).__name__, e))
             torch.cuda.synchronize()
-    if not graphed:
+    if full and not graphed:
         _C.kernel_timer = _C.KernelTimer(watch=watch)
-    t = timed(run, steps, 0, world, tag)
+    t = timed(run, steps, 0, world, tag, keep)
     note("%s timed region done (%s)" % (tag, "graph replay" if graphed else "eager"))
+    if keep is not None:
+        keep["arrays"] = host_arrays(infer_outputs(*keep.pop("last")))
+    if not full:
+        del model
+        return t, None
     summary = dict(probe)
     if not graphed:
         summary.update(_C.kernel_timer.summary())          # dominant shapes: the timed region's own durations
@@ -513,7 +615,10 @@ def offset_field_points(dev, contraction="auto", n=40):
             "points": out}
 
 
-def train_leg(args, dev, world, rank, steps, warmup, cfg="3"):
+def train_leg(args, dev, world, rank, steps, warmup, cfg="3", full=True, keep=None):
+    """Times the training step.  `full`: two more (untimed) steps with HIP events around the DCNv2 / convolution
+    launches for the rooflines (the summary; None otherwise).  `keep`: a dict that receives the last timed step's
+    outputs as host arrays (`train_outputs`)."""
     import torch
     from centerpoly_amd import _C, synth
     from centerpoly_amd.opts import opts
@@ -537,10 +642,15 @@ def train_leg(args, dev, world, rank, steps, warmup, cfg="3"):
     batch = {k: torch.from_numpy(v).to(dev) for k, v in nb.items()}    # resident before timing
 
     def step():
-        trainer.step(batch, train=True)
+        return trainer.step(batch, train=True)
 
-    t = timed(step, steps, warmup, world, "train(cfg %s)" % cfg)
+    t = timed(step, steps, warmup, world, "train(cfg %s)" % cfg, keep)
     note("train timed region done")
+    if keep is not None:
+        keep["arrays"] = host_arrays(train_outputs(keep.pop("last"), model))
+    if not full:
+        del trainer, model, optimizer, batch
+        return t, None, B, (in_h, in_w, npts)
     # the DCNv2 launches of two more (untimed) steps, HIP-event timed on rank 0; with the timer on,
     # the backward entry point is called once per gradient group (data / weight / bias)
     if rank == 0:
@@ -782,6 +892,13 @@ def compact_line(line):
     return text
 
 
+def write_outputs(args, keep):
+    """--dump-outputs: the last timed step's host arrays (rank 0 only) to the folder the option names."""
+    if keep is not None:
+        manifest = dump_outputs(keep.pop("arrays"), args.dump_outputs)
+        note("outputs of the last timed step: %s (%s)" % (args.dump_outputs, ", ".join(sorted(manifest))))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
@@ -821,19 +938,27 @@ def main(argv=None):
     line = {"n_gpus": world, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": arithmetic.describe(), "arithmetic": args.arithmetic,
             "data": "synthetic (counter-hash inputs, name-hashed random-init weights)"}
+    keep = {} if args.dump_outputs and rank == 0 else None
     if mode == "infer":
         if cfg == "4":
             heads = {"hm": 8, "poly": 48, "pseudo_depth": 1, "reg": 2}
             t, summary = infer_leg(args, dev, world, arch="hourglass", heads=heads, rep="polar",
-                                   offset_weight_scale=1.0)
+                                   offset_weight_scale=1.0, full=args.full, keep=keep)
             workload = ("BASELINE config 4: Hourglass-104 (2 stacks), 1x3x%dx%d synthetic, 24-vertex polar head, "
                         "K=128, forward + sigmoid + NMS/top-k/decode" % (args.height, args.width))
             metric = "inference img/s @2048x1024 Hourglass-104 (1 GPU)"
         else:
-            t, summary = infer_leg(args, dev, world)
+            t, summary = infer_leg(args, dev, world, full=args.full, keep=keep)
             workload = ("BASELINE config 2: DLA-34 + DCNv2, 1x3x%dx%d synthetic, 16-vertex cartesian head, "
                         "K=128, forward + sigmoid + NMS/top-k/decode" % (args.height, args.width))
             metric = "inference img/s @2048x1024 DLA-34 (1 GPU)"
+        line.update({
+            "metric": metric, "unit": "img/s",
+            "value": world * args.steps / t, "ms_per_step": 1e3 * t / args.steps,
+            "config": {"workload": workload, "images_per_step": world,
+                       "parallelism": "replicas" if world > 1 else "single"}})
+        write_outputs(args, keep)
+    if mode == "infer" and args.full:
         meta = summary.pop("__meta__")
         hbm, mfma = dcn_roofline(summary, fwd_contraction=infer_contraction(args))
         chbm, cmfma = conv_roofline(summary)
@@ -841,10 +966,6 @@ def main(argv=None):
         if mfma is None:                                   # Hourglass: no DCN, the 3x3 convolution dominates
             hbm, mfma = chbm, cmfma
         line.update({
-            "metric": metric, "unit": "img/s",
-            "value": world * args.steps / t, "ms_per_step": 1e3 * t / args.steps,
-            "config": {"workload": workload, "images_per_step": world,
-                       "parallelism": "replicas" if world > 1 else "single"},
             # `roofline` is the north star's figure -- the dominant DCNv2 forward launch against HBM (algorithmic
             # bytes of SURVEY 8(d) / HIP-event launch time / 8 TB/s); `roofline_mfma` prices the same launch's
             # algorithmic flops against the matrix pipe it issues on (the issued flops are `issued_frac`)
@@ -896,8 +1017,9 @@ def main(argv=None):
                                      **train_rooflines(ts))
             if not args.no_other_configs:
                 line["other_configs"] = other_config_points(args, dev)
-    else:
-        t, summary, B, (in_h, in_w, npts) = train_leg(args, dev, world, rank, args.steps, args.warmup, cfg=cfg)
+    if mode == "train":
+        t, summary, B, (in_h, in_w, npts) = train_leg(args, dev, world, rank, args.steps, args.warmup, cfg=cfg,
+                                                      full=args.full, keep=keep)
         line.update({
             "metric": "train img/s 1/2/4/8 GPU @%dx%d DLA-34" % (in_w, in_h), "unit": "img/s",
             "value": world * B * args.steps / t, "ms_per_step": 1e3 * t / args.steps,
@@ -910,12 +1032,14 @@ def main(argv=None):
             "scaling_base": "weak scaling of the training leg: compare with the N=1 line's "
                             "train.value (same %d img/GPU workload), not with its inference value" % B,
         })
-        if rank == 0:
+        write_outputs(args, keep)
+        if rank == 0 and args.full:
             line.update(train_rooflines(summary))      # forward (`roofline`) and both backward kernels
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args)
-        line["detail"] = write_detail(line, args)
+        if args.full:
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(args)
+            line["detail"] = write_detail(line, args)
         print(compact_line(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -1,6 +1,9 @@
-"""bench.py contract checks that need no GPU: argument defaults and the JSON line's shape."""
+"""bench.py contract checks: argument defaults, the JSON line's shape and the output dump need no GPU; one GPU test
+runs the plain path end to end."""
 import ast
 import os
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -135,3 +138,101 @@ def test_split_bf16_roofline_prices_algorithmic_flops():
     r = bench.split_bf16_roofline({}, 9.66e9, 50e-6)
     assert abs(r["frac"] - 9.66e9 / 50e-6 / 2.5e15) < 1e-9
     assert abs(r["issued_frac"] - 3 * r["frac"]) < 1e-12
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    """A plain run measures the headline only; everything beside it waits for --full; --steps is the timed count."""
+    import pytest
+    bench = _bench()
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (3, 1)
+    b = bench.parse(["--full", "--dump-outputs", "outs"])
+    assert b.full is True and b.dump_outputs == "outs"
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_outputs_keeps_the_budget_and_samples_reproducibly(tmp_path):
+    """Small arrays are written whole (float32, float64 kept), the ones that do not fit as a seeded sample of their
+    flattened elements that the manifest's rule reproduces; the files stay under the byte limit; two dumps agree."""
+    import numpy as np
+    import torch
+    bench = _bench()
+    rng = np.random.default_rng(1)
+    arrays = bench.host_arrays({"small": torch.arange(20, dtype=torch.int64).reshape(4, 5),
+                                "scalar": torch.tensor(1.5), "wide": rng.standard_normal(10),
+                                "big": rng.standard_normal((3, 100000)).astype(np.float32),
+                                "bigger": rng.standard_normal(500000).astype(np.float32)})
+    assert arrays["small"].dtype == np.float32 and arrays["wide"].dtype == np.float64
+    limit = 1 << 20
+    man = bench.dump_outputs(arrays, str(tmp_path / "a"), limit=limit)
+    bench.dump_outputs(arrays, str(tmp_path / "b"), limit=limit)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["big.npy", "bigger.npy", "manifest.json", "scalar.npy", "small.npy", "wide.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files if f.endswith(".npy")) <= limit
+    for f in files:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes(), f
+    for k in ("small", "scalar", "wide"):
+        assert "sample" not in man[k] and np.array_equal(np.load(tmp_path / "a" / (k + ".npy")), arrays[k])
+    for k in ("big", "bigger"):
+        e = man[k]
+        assert e["shape"] == list(arrays[k].shape) and 0 < e["sample"] < arrays[k].size
+        idx = np.sort(np.random.default_rng(e["sample_seed"]).integers(0, arrays[k].size, e["sample"]))
+        assert np.array_equal(np.load(tmp_path / "a" / (k + ".npy")), arrays[k].reshape(-1)[idx])
+    assert man["big"]["sample"] == man["bigger"]["sample"]       # the budget left is shared evenly
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --steps 3 --warmup 1 --dump-outputs DIR` on a small input: one JSON line with the headline keys and
+    nothing of --full, and DIR holds the detections and head maps of the last timed step."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    out = tmp_path / "outs"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--height", "256", "--width", "512", "--dump-outputs", str(out)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    lines = p.stdout.decode().strip().splitlines()
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert (line["steps"], line["warmup"], line["n_gpus"], line["unit"]) == (3, 1, 1, "img/s")
+    assert line["higher_is_better"] is True and "DLA-34" in line["metric"] and line["dtype"]
+    assert abs(line["value"] * line["ms_per_step"] - 1e3) < 1e-3 * 1e3
+    for k in ("roofline", "roofline_mfma", "train", "cpu_baseline", "other_configs", "detail"):
+        assert k not in line, k
+    man = json.load(open(str(out / "manifest.json")))
+    assert set(man) == {"dets", "head_hm", "head_poly", "head_pseudo_depth", "head_reg"}
+    assert not any("sample" in e for e in man.values())
+    dets = np.load(str(out / "dets.npy"))
+    hm = np.load(str(out / "head_hm.npy"))
+    assert dets.dtype == np.float32 and dets.shape[:2] == (1, 128) and np.isfinite(dets).all()
+    assert hm.shape == (1, 8, 64, 128) and hm.min() >= 0.0 and hm.max() <= 1.0        # the activated heat map
+    assert np.load(str(out / "head_poly.npy")).shape == (1, 32, 64, 128)
+
+
+def test_bench_starts_from_a_read_only_tree():
+    """The benchmark may run from a checkout its user cannot write to: importing it must not need to create anything
+    in the tree (MIOpen then keeps its default per-user cache).  Directory creation under the tree is made to fail."""
+    import subprocess
+    import sys
+    code = ("import os, sys\n"
+            "root = %r\n"
+            "real = os.makedirs\n"
+            "def makedirs(p, *a, **k):\n"
+            "    if os.path.abspath(p).startswith(root + os.sep):\n"
+            "        raise PermissionError(13, 'Permission denied', p)\n"
+            "    return real(p, *a, **k)\n"
+            "os.makedirs = makedirs\n"
+            "for v in ('MIOPEN_CUSTOM_CACHE_DIR', 'MIOPEN_USER_DB_PATH'):\n"
+            "    os.environ.pop(v, None)\n"
+            "sys.path.insert(0, root)\n"
+            "import bench\n"
+            "assert bench.parse(['--gpus', '1', '--steps', '2', '--warmup', '1']).steps == 2\n"
+            "assert not any(os.environ.get(v, '').startswith(root) for v in ('MIOPEN_CUSTOM_CACHE_DIR', "
+            "'MIOPEN_USER_DB_PATH'))\n"
+            "print('ok')\n") % ROOT
+    p = subprocess.run([sys.executable, "-c", code], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert p.returncode == 0 and p.stdout.strip() == b"ok", p.stderr.decode()[-1500:]

@@ -14,7 +14,8 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_ANN = "/root/reference/KITTIPolyStuff/BBoxes"
+# the reference's own KITTI annotations (KITTIPolyStuff/BBoxes/val16.json), stored as a fixture
+REF_ANN = os.path.join(ROOT, "tests", "golden", "kitti_bboxes")
 
 
 def test_reference_import_lines_resolve_after_install():
@@ -82,7 +83,6 @@ def test_real_dataset_names_refuse_missing_data(tmp_path):
         get_dataset("coco", "polydet")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_ANN), reason="the reference's annotation files are not on this box")
 def test_kitti_annotations_are_read_and_sampled(tmp_path):
     """The reference's own val16.json through the JSON index and the host half of the sampler; images are
     generated PNG files (the dataset's images are not available offline)."""

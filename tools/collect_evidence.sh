@@ -40,7 +40,8 @@ run() {
 want() { case " $steps " in *" $1 "*) return 0;; *) return 1;; esac; }
 
 if want bench; then
-  run bench "$P/${tag}_bench_n1.json" -- bash -c "timeout -k 10 900 python3 bench.py > gpurun_out/${tag}_bench_stdout.txt 2> gpurun_out/${tag}_bench_n1.err && tail -1 gpurun_out/${tag}_bench_stdout.txt > $P/${tag}_bench_n1.json && cp gpurun_out/bench_detail.json $P/${tag}_bench_n1_detail.json && test \$(wc -c < $P/${tag}_bench_n1.json) -lt 8000"
+  o=$(dirname "$P")        # the output folder: bench.py --full writes its detail file there as well
+  run bench "$P/${tag}_bench_n1.json" -- bash -c "timeout -k 10 900 python3 bench.py --full > $o/${tag}_bench_stdout.txt 2> $o/${tag}_bench_n1.err && tail -1 $o/${tag}_bench_stdout.txt > $P/${tag}_bench_n1.json && cp $o/bench_detail.json $P/${tag}_bench_n1_detail.json && test \$(wc -c < $P/${tag}_bench_n1.json) -lt 8000"
 fi
 if want infer; then
   run infer "$P/${tag}_infer_kernel_stats.csv" "$P/${tag}_infer_by_launch_shape.csv" -- bash -c "tools/run_infer_prof.sh $tag && cp gpurun_out/prof_infer_$tag/infer_kernel_stats.csv $P/${tag}_infer_kernel_stats.csv && python3 tools/by_launch_shape.py gpurun_out/prof_infer_$tag/infer_kernel_trace.csv > $P/${tag}_infer_by_launch_shape.csv"

@@ -44,7 +44,7 @@ for (kern, grid), shape in SHAPES.items():
         layers["%dx%dx%dx%dx%d" % shape] = (2.0 * f + w) * 1024.0
         raw["%dx%dx%dx%dx%d" % shape] = {"FETCH_SIZE_KB_avg": f, "WRITE_SIZE_KB_avg": w, "launches": n}
 out = {"kernel_rev": bench.kernel_revision(), "inputs": "bench.py infer leg",
-       "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE --output-format csv -- python3 bench.py "
+       "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE --output-format csv -- python3 bench.py --full "
                   "--config 2 --steps 3 --warmup 2 --no_cpu_baseline --no_train_point --no_detector_point "
                   "--no_offset_points --no_other_configs --no_exact_point (separate passes)",
        "correction": "traffic = (2*FETCH_SIZE + WRITE_SIZE)*1024 bytes (gfx950: FETCH_SIZE reports half of a wide coalesced "

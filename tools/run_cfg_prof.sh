@@ -9,7 +9,7 @@ tag=${2:-r03}
 out=gpurun_out/prof_cfg${cfg}_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-args="--config $cfg --steps 6 --warmup 2 --no_cpu_baseline"
+args="--full --config $cfg --steps 6 --warmup 2 --no_cpu_baseline"
 timeout -k 10 600 python3 bench.py $args > $out/warm.json 2> $out/warm.err
 echo "warm rc=$?"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out -o cfg$cfg -- python3 bench.py $args > $out/bench.json 2> $out/bench.err

@@ -6,7 +6,7 @@ tag=${1:-r03}
 out=gpurun_out/pmc_bench_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-B="python3 bench.py --config 2 --steps 3 --warmup 2 --no_cpu_baseline --no_train_point --no_detector_point --no_offset_points --no_other_configs --no_exact_point"
+B="python3 bench.py --full --config 2 --steps 3 --warmup 2 --no_cpu_baseline --no_train_point --no_detector_point --no_offset_points --no_other_configs --no_exact_point"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 400 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $out/$c -o $c -- $B > $out/$c.log 2>&1
   rc=$?; echo "pass $c rc=$rc"

@@ -9,9 +9,9 @@ mkdir -p $out
 export TMPDIR=/tmp
 # PMC_LEG=train: the B = 4 training leg instead (the inference leg shrunk to one step)
 if [ "${PMC_LEG:-infer}" = train ]; then
-  B="python3 bench.py --config 2 --steps 1 --warmup 1 --no_cpu_baseline --no_detector_point --no_offset_points --no_other_configs --no_exact_point"
+  B="python3 bench.py --full --config 2 --steps 1 --warmup 1 --no_cpu_baseline --no_detector_point --no_offset_points --no_other_configs --no_exact_point"
 else
-  B="python3 bench.py --config 2 --steps 3 --warmup 2 --no_cpu_baseline --no_train_point --no_detector_point --no_offset_points --no_other_configs --no_exact_point"
+  B="python3 bench.py --full --config 2 --steps 3 --warmup 2 --no_cpu_baseline --no_train_point --no_detector_point --no_offset_points --no_other_configs --no_exact_point"
 fi
 timeout -k 10 500 rocprofv3 --kernel-trace --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_WAIT_INST_ANY --output-format csv -d $out/p1 -o p1 -- $B > $out/p1.log 2>&1
 rc=$?; echo "pass rc=$rc"
