@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libcenterpoly_hip.so")
 
 CP_OK = 0
 REP = {"cartesian": 0, "polar": 1, "polar_fixed": 2}
+HEATMAP_UMICH, HEATMAP_ELLIPSE = 0, 1           # CP_HEATMAP_* of cp_polydet_targets_ex
 L1_PLAIN, L1_POLAR, L1_POLAR_FIXED, L1_RELU20, L1_SMOOTH = 0, 1, 2, 3, 4
 DCN_BWD_EXACT_F32, DCN_BWD_NARROW_TILES, DCN_BWD_ROUND1_KERNELS = 1, 2, 4
 DCN_CONTRACTION = {"f32": 0, "bf16x3": 1, "bf16x3_region": 3}     # (+1 = "..._PREPARED": weights already in the workspace)
@@ -74,6 +75,7 @@ _SIGNATURES = {
     "cp_polydet_post_process": (c_int32, [_P, _P, c_float, c_int32, c_int32, c_int32, _P, _P]),
     "cp_polydet_targets_workspace_bytes": (c_size_t, [POINTER(TargetShape)]),
     "cp_polydet_targets": (c_int32, [POINTER(TargetShape)] + [_P] * 19 + [_P, c_size_t, _P]),
+    "cp_polydet_targets_ex": (c_int32, [POINTER(TargetShape), c_int32] + [_P] * 19 + [_P, c_size_t, _P]),
     "cp_polydet_dense_targets": (c_int32, [POINTER(TargetShape), _P, _P, c_size_t, _P, _P, _P]),
     "cp_conv_direct_supported": (c_int32, [c_int32] * 5),
     "cp_conv_direct_wgrad_supported": (c_int32, [c_int32] * 5),

@@ -2,19 +2,22 @@
 //
 // Replaces the per-object Python loop of PolydetDataset.__getitem__
 // (reference: src/lib/datasets/sample/polydet.py:160-405) and the helpers it calls --
-// affine_transform, gaussian_radius, gaussian2D, draw_umich_gaussian
-// (src/lib/utils/image.py:62-65, 95-141): from the raw annotations of a batch (COCO boxes,
-// polygon vertices, class ids) and each image's output affine it writes the heat maps and the
-// per-object regression targets the loss consumes (batch schema of :425-449).
+// affine_transform, gaussian_radius, gaussian2D, draw_umich_gaussian, and with `--elliptical_gt`
+// gaussian_ellipse_2d / draw_ellipse_gaussian (src/lib/utils/image.py:62-65, 95-173): from the
+// raw annotations of a batch (COCO boxes, polygon vertices, class ids) and each image's output
+// affine it writes the heat maps and the per-object regression targets the loss consumes (batch
+// schema of :425-449).
 //
 //   targets_object_kernel   one workgroup per image, one lane per object slot: flip + vertex
 //                           re-ordering, affine + clip of every vertex and of the box, Gaussian
-//                           radius, mass centre, ind / reg / peak / wh / poly (cartesian or
-//                           polar) / reg_mask, and the image's mean class frequency.  float64
+//                           radius (and the ellipse radii of --elliptical_gt), mass centre,
+//                           ind / reg / peak / wh / poly (cartesian or polar) / reg_mask, and
+//                           the image's mean class frequency.  float64
 //                           where the reference computes in Python floats, float32 where it
 //                           stores into float32 arrays, no fma contraction.
-//   targets_splat_kernel    one workgroup per (object, splat): the (2r+1)^2 Gaussian of the
-//                           centre into hm[class] and of every vertex into border_hm,
+//   targets_splat_kernel    one workgroup per (object, splat): the (2r+1)^2 Gaussian (or the
+//                           (2ry+1) x (2rx+1) ellipse) of the centre into hm[class] and the
+//                           (2r+1)^2 Gaussian of every vertex into border_hm,
 //                           max-composited with an integer atomicMax on the fp32 bit pattern
 //                           (values are >= 0, so the order of objects does not matter --
 //                           exactly np.maximum's result).
@@ -46,12 +49,46 @@ struct TargetArgs {
   float* reg;               // [B][M][2]
   float* wh;                // [B][M][2]
   float* freq_mask;         // [B]
-  int* desc;                // workspace [B][M][4 + 2N]: valid, cls, cx, cy | radius in [3]... see below
-  int B, M, N, C, h, w, rep, no_reorder_flip;
+  int* desc;                // workspace [B][M][7 + 2N], see below
+  int B, M, N, C, h, w, rep, no_reorder_flip, heatmap;
 };
 
-// desc row layout (ints): [0] radius or -1 (invalid), [1] class, [2] cx, [3] cy, [4 + 2i], [5 + 2i] vertex i
-__device__ __forceinline__ int desc_stride(int N) { return 4 + 2 * N; }
+// desc row layout (ints): [0] radius or -1 (invalid), [1] class, [2] cx, [3] cy, [4] rx, [5] ry of the centre splat
+// (both = radius for CP_HEATMAP_UMICH), [6] the call's CP_HEATMAP_* (what cp_polydet_dense_targets replays),
+// [7 + 2i], [8 + 2i] vertex i
+__device__ __forceinline__ int desc_stride(int N) { return 7 + 2 * N; }
+
+// draw_umich_gaussian's value at offset (dx, dy) of a radius-r splat (gaussian2D, utils/image.py:118-124)
+__device__ __forceinline__ double umich_value(int dx, int dy, int r) {
+  const double diameter = (double)(2 * r + 1);
+  const double sigma = diameter / 6;
+  const double denom = 2 * sigma * sigma;
+  const double x = (double)dx, y = (double)dy;
+  double g = exp(-(x * x + y * y) / denom);
+  if (g < 2.220446049250313e-16) g = 0.0;   // h[h < eps * h.max()] = 0, h.max() == 1
+  return g;
+}
+
+// gaussian_ellipse_2d (utils/image.py:144-156) at row offset dy, column offset dx of a (2ry+1) x (2rx+1) grid: the
+// reference's "y_modifier" (2rx+1)/m scales the ROW offset, its "x_modifier" (2ry+1)/m the column offset; float64 in
+// its order of operations, no epsilon cut
+__device__ __forceinline__ double ellipse_value(int dx, int dy, int rx, int ry) {
+  const double m = (double)max(2 * rx + 1, 2 * ry + 1);
+  const double mr = (double)(2 * rx + 1) / m, mc = (double)(2 * ry + 1) / m;
+  const double sigma = (double)(2 * min(rx, ry) + 1) / 6;
+  const double a = (double)dy * mr, b = (double)dx * mc;
+  return exp(-((a * a + b * b) / (2 * (sigma * sigma))));
+}
+
+// the splat window of draw_*_gaussian around (cx, cy) with half-extents (rx, ry), clipped to the map; false when empty
+__device__ __forceinline__ bool splat_window(int cx, int cy, int rx, int ry, int w, int h, int& left, int& right,
+                                             int& top, int& bottom) {
+  left = min(cx, rx);
+  right = min(w - cx, rx + 1);
+  top = min(cy, ry);
+  bottom = min(h - cy, ry + 1);
+  return left + right > 0 && top + bottom > 0 && cx - left >= 0 && cy - top >= 0;
+}
 
 // index into the un-reordered (already mirrored) vertex list that lands at position j after
 // the reference's two re-ordering loops (polydet.py:181-187); Python negative indices wrap
@@ -148,6 +185,14 @@ __global__ __launch_bounds__(1024) void targets_object_kernel(TargetArgs a) {
       if (hh > 0.f && ww > 0.f) {
         const double rad_d = gaussian_radius_d((long long)ceilf(hh), (long long)ceilf(ww));
         const int radius = max(0, (int)rad_d);
+        // sample/polydet.py:223-225: radius_x = r if h > w else int(r * (w / h)), radius_y = r if w >= h else
+        // int(r * (h / w)) -- float32 ratio and product (numpy scalars), truncated.  (Capped far beyond any map so
+        // that 2 r + 1 stays in int range; the reference could not allocate such a grid.)
+        int rx = radius, ry = radius;
+        if (a.heatmap == CP_HEATMAP_ELLIPSE) {
+          if (!(hh > ww)) rx = (int)fminf((float)radius * (ww / hh), 16777216.f);
+          if (!(ww >= hh)) ry = (int)fminf((float)radius * (hh / ww), 16777216.f);
+        }
         double mx = 0.0, my = 0.0;
         for (int i = 0; i < a.N; ++i) {
           double x, y;
@@ -161,13 +206,16 @@ __global__ __launch_bounds__(1024) void targets_object_kernel(TargetArgs a) {
         desc[1] = a.cls_id[row];
         desc[2] = cxi;
         desc[3] = cyi;
+        desc[4] = rx;
+        desc[5] = ry;
+        desc[6] = a.heatmap;
         a.wh[2 * row] = ww;
         a.wh[2 * row + 1] = hh;
         for (int i = 0; i < a.N; ++i) {
           double x, y;
           point(i, x, y);
-          desc[4 + 2 * i] = (int)x;
-          desc[5 + 2 * i] = (int)y;
+          desc[7 + 2 * i] = (int)x;
+          desc[8 + 2 * i] = (int)y;
           const double dx = x - (double)ctx, dy = y - (double)cty;
           if (a.rep == CP_REP_CARTESIAN) {
             poly_o[2 * i] = (float)dx;
@@ -216,32 +264,32 @@ __global__ __launch_bounds__(256) void targets_splat_kernel(TargetArgs a) {
   if (radius < 0) return;
   const int b = row / a.M;
   float* plane;
-  int x, y;
+  int x, y, rx = radius, ry = radius;
+  bool ellipse = false;
   if (s == 0) {
     const int cls = desc[1];
     if (cls < 0 || cls >= a.C) return;
     plane = a.hm + ((long long)b * a.C + cls) * a.h * a.w;
     x = desc[2];
     y = desc[3];
+    ellipse = desc[6] == CP_HEATMAP_ELLIPSE;   // (border_hm keeps the UMich splats: sample/polydet.py:236)
+    if (ellipse) {
+      rx = desc[4];
+      ry = desc[5];
+    }
   } else {
     if (!a.border_hm) return;
     plane = a.border_hm + (long long)b * a.h * a.w;
-    x = desc[4 + 2 * (s - 1)];
-    y = desc[5 + 2 * (s - 1)];
+    x = desc[7 + 2 * (s - 1)];
+    y = desc[8 + 2 * (s - 1)];
   }
-  const int left = min(x, radius), right = min(a.w - x, radius + 1);
-  const int top = min(y, radius), bottom = min(a.h - y, radius + 1);
+  int left, right, top, bottom;
+  if (!splat_window(x, y, rx, ry, a.w, a.h, left, right, top, bottom)) return;
   const int nx = left + right, ny = top + bottom;
-  if (nx <= 0 || ny <= 0 || x - left < 0 || y - top < 0) return;
-  const double diameter = (double)(2 * radius + 1);
-  const double sigma = diameter / 6;
-  const double denom = 2 * sigma * sigma;
   for (int e = threadIdx.x; e < nx * ny; e += 256) {
     const int iy = e / nx, ix = e - iy * nx;
-    const double dx = (double)(ix - left), dy = (double)(iy - top);
-    double g = exp(-(dx * dx + dy * dy) / denom);
-    if (g < 2.220446049250313e-16) g = 0.0;   // h[h < eps * h.max()] = 0, h.max() == 1
-    const float v = (float)g;
+    const int dx = ix - left, dy = iy - top;
+    const float v = (float)(ellipse ? ellipse_value(dx, dy, rx, ry) : umich_value(dx, dy, radius));
     atomicMax(reinterpret_cast<unsigned*>(plane + (long long)(y - top + iy) * a.w + (x - left + ix)),
               __float_as_uint(v));
   }
@@ -252,6 +300,9 @@ __global__ __launch_bounds__(256) void targets_splat_kernel(TargetArgs a) {
 // 0..k.  One thread per pixel replays the objects in order with a running class-maximum: float64 Gaussian (the splat's
 // own expression) against the float32 map value -- so where object k itself sets the maximum the test is
 // g >= float32(g), true only when the rounding to float32 went down (the reference's behaviour, reproduced).
+// With --elliptical_gt (desc[6] == CP_HEATMAP_ELLIPSE) the running maximum rises by what the object drew into hm -- the
+// ellipse, over its own (wider) window -- while the ownership test keeps draw_dense_reg's UMich Gaussian and window of
+// the plain radius (utils/image.py:176-204 is called with `radius` in both modes).
 __global__ __launch_bounds__(256) void targets_dense_kernel(const int* __restrict__ desc_all, const float* __restrict__ poly,
                                                             float* __restrict__ dense, float* __restrict__ dmask, int M,
                                                             int N, int h, int w) {
@@ -267,17 +318,16 @@ __global__ __launch_bounds__(256) void targets_dense_kernel(const int* __restric
     const int radius = desc[0];
     if (radius < 0) continue;
     const int cx = desc[2], cy = desc[3];
-    const int left = min(cx, radius), right = min(w - cx, radius + 1);
-    const int top = min(cy, radius), bottom = min(h - cy, radius + 1);
-    if (left + right <= 0 || top + bottom <= 0 || cx - left < 0 || cy - top < 0) continue;
+    const bool ellipse = desc[6] == CP_HEATMAP_ELLIPSE;
+    int left, right, top, bottom;
+    if (ellipse && splat_window(cx, cy, desc[4], desc[5], w, h, left, right, top, bottom) && x >= cx - left &&
+        x < cx + right && y >= cy - top && y < cy + bottom)
+      run_max = fmaxf(run_max, (float)ellipse_value(x - cx, y - cy, desc[4], desc[5]));   // hm.max(axis=0) after the
+                                                                                         // object's draw
+    if (!splat_window(cx, cy, radius, radius, w, h, left, right, top, bottom)) continue;
     if (x < cx - left || x >= cx + right || y < cy - top || y >= cy + bottom) continue;
-    const double diameter = (double)(2 * radius + 1);
-    const double sigma = diameter / 6;
-    const double denom = 2 * sigma * sigma;
-    const double dx = (double)(x - cx), dy = (double)(y - cy);
-    double g = exp(-(dx * dx + dy * dy) / denom);
-    if (g < 2.220446049250313e-16) g = 0.0;
-    run_max = fmaxf(run_max, (float)g);                  // hm.max(axis=0) after draw_gaussian(hm[cls], ...)
+    const double g = umich_value(x - cx, y - cy, radius);
+    if (!ellipse) run_max = fmaxf(run_max, (float)g);    // hm.max(axis=0) after draw_gaussian(hm[cls], ...)
     if (g >= (double)run_max) cur = k;
   }
   const long long plane = (long long)h * w;
@@ -307,18 +357,19 @@ extern "C" int cp_polydet_dense_targets(const cp_target_shape* s, const float* p
 
 extern "C" size_t cp_polydet_targets_workspace_bytes(const cp_target_shape* s) {
   if (!s || s->B <= 0 || s->max_objs <= 0 || s->nbr_points <= 0) return 0;
-  return cp_align_up((size_t)s->B * s->max_objs * (4 + 2 * (size_t)s->nbr_points) * sizeof(int), 256);
+  return cp_align_up((size_t)s->B * s->max_objs * (7 + 2 * (size_t)s->nbr_points) * sizeof(int), 256);
 }
 
-extern "C" int cp_polydet_targets(const cp_target_shape* s, const double* bbox_xywh,
-                                  const double* poly_xy, const int32_t* cls_id,
-                                  const float* pseudo_depth_in, const float* class_freq,
-                                  const int32_t* num_objs, const uint8_t* flipped,
-                                  const int32_t* img_width, const double* trans_output, float* hm,
-                                  float* border_hm, uint8_t* reg_mask, int64_t* ind, float* poly,
-                                  float* pseudo_depth, float* peak, float* reg, float* wh,
-                                  float* freq_mask, void* workspace, size_t workspace_bytes,
-                                  void* stream) {
+extern "C" int cp_polydet_targets_ex(const cp_target_shape* s, int32_t heatmap, const double* bbox_xywh,
+                                     const double* poly_xy, const int32_t* cls_id,
+                                     const float* pseudo_depth_in, const float* class_freq,
+                                     const int32_t* num_objs, const uint8_t* flipped,
+                                     const int32_t* img_width, const double* trans_output, float* hm,
+                                     float* border_hm, uint8_t* reg_mask, int64_t* ind, float* poly,
+                                     float* pseudo_depth, float* peak, float* reg, float* wh,
+                                     float* freq_mask, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+  CP_CHECK_ARG(heatmap == CP_HEATMAP_UMICH || heatmap == CP_HEATMAP_ELLIPSE);
   CP_CHECK_ARG(s && bbox_xywh && poly_xy && cls_id && pseudo_depth_in && class_freq && num_objs);
   CP_CHECK_ARG(flipped && img_width && trans_output && hm && reg_mask && ind && poly);
   CP_CHECK_ARG(pseudo_depth && peak && reg && wh && freq_mask);
@@ -335,7 +386,7 @@ extern "C" int cp_polydet_targets(const cp_target_shape* s, const double* bbox_x
   a.ind = (long long*)ind; a.poly = poly; a.pseudo_depth = pseudo_depth; a.peak = peak; a.reg = reg;
   a.wh = wh; a.freq_mask = freq_mask; a.desc = (int*)workspace;
   a.B = s->B; a.M = s->max_objs; a.N = s->nbr_points; a.C = s->num_classes; a.h = s->out_h;
-  a.w = s->out_w; a.rep = s->rep; a.no_reorder_flip = s->no_reorder_flip;
+  a.w = s->out_w; a.rep = s->rep; a.no_reorder_flip = s->no_reorder_flip; a.heatmap = heatmap;
   const size_t plane = (size_t)s->out_h * s->out_w * sizeof(float);
   if (hipMemsetAsync(hm, 0, (size_t)s->B * s->num_classes * plane, st) != hipSuccess) return CP_EHIP;
   if (border_hm && hipMemsetAsync(border_hm, 0, (size_t)s->B * plane, st) != hipSuccess) return CP_EHIP;
@@ -343,4 +394,18 @@ extern "C" int cp_polydet_targets(const cp_target_shape* s, const double* bbox_x
   hipLaunchKernelGGL(targets_object_kernel, dim3(s->B), dim3(threads), 0, st, a);
   hipLaunchKernelGGL(targets_splat_kernel, dim3(s->B * s->max_objs, 1 + s->nbr_points), dim3(256), 0, st, a);
   return cp_launch_status();
+}
+
+extern "C" int cp_polydet_targets(const cp_target_shape* s, const double* bbox_xywh,
+                                  const double* poly_xy, const int32_t* cls_id,
+                                  const float* pseudo_depth_in, const float* class_freq,
+                                  const int32_t* num_objs, const uint8_t* flipped,
+                                  const int32_t* img_width, const double* trans_output, float* hm,
+                                  float* border_hm, uint8_t* reg_mask, int64_t* ind, float* poly,
+                                  float* pseudo_depth, float* peak, float* reg, float* wh,
+                                  float* freq_mask, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  return cp_polydet_targets_ex(s, CP_HEATMAP_UMICH, bbox_xywh, poly_xy, cls_id, pseudo_depth_in, class_freq, num_objs,
+                               flipped, img_width, trans_output, hm, border_hm, reg_mask, ind, poly, pseudo_depth,
+                               peak, reg, wh, freq_mask, workspace, workspace_bytes, stream);
 }

@@ -5,7 +5,7 @@ PolydetDataset.__getitem__ (src/lib/datasets/sample/polydet.py:160-405, helpers 
 src/lib/utils/image.py:62-65,95-141).  Here a loader worker only PACKS the raw annotations of
 an image into flat arrays (`pack_annotations`, host, no arithmetic); after the batch reached
 the GPU `build_targets` turns them into the batch dict of :425-449 with two HIP kernels
-(cp_polydet_targets): hm, reg_mask, ind, poly, pseudo_depth, freq_mask, border_hm, wh, peak, reg.
+(cp_polydet_targets_ex): hm, reg_mask, ind, poly, pseudo_depth, freq_mask, border_hm, wh, peak, reg.
 """
 import numpy as np
 import torch
@@ -43,13 +43,15 @@ def collate(packed):
 
 
 def build_targets(raw, output_h, output_w, num_classes, rep="cartesian", no_reorder_flip=False,
-                  with_border_hm=True, dense_poly=False, cat_spec_poly=False):
+                  with_border_hm=True, dense_poly=False, cat_spec_poly=False, elliptical_gt=False):
     """raw: dict of DEVICE tensors with the keys of pack_annotations, batched on dim 0.
     Returns the batch dict (device tensors) the polydet loss consumes.
     dense_poly (`--dense_poly`, sample/polydet.py:401-403,429-441): adds 'dense_poly' / 'dense_poly_mask' [B,2N,h,w]
     (cp_polydet_dense_targets) and drops 'poly', as the reference's dict does.  cat_spec_poly (:245-248,288-291,424-425):
     adds 'cat_spec_poly' / 'cat_spec_mask' [B,M,C*2N] -- every object's polygon row in its class's block -- and drops
-    the keys the reference's cat-spec dict lacks (freq_mask, border_hm, wh)."""
+    the keys the reference's cat-spec dict lacks (freq_mask, border_hm, wh).  elliptical_gt (`--elliptical_gt`,
+    :156-159,223-228, utils/image.py:144-173): the centre heat map hm is draw_ellipse_gaussian's, stretched along the
+    longer box side (CP_HEATMAP_ELLIPSE); border_hm and draw_dense_reg's ownership window keep the plain radius."""
     bbox = raw["bbox"]
     if not bbox.is_cuda:
         raise _C.NativeError("build_targets needs HIP device tensors (got %s); there is no CPU "
@@ -77,13 +79,14 @@ def build_targets(raw, output_h, output_w, num_classes, rep="cartesian", no_reor
     lib = _C.lib()
     nws = lib.cp_polydet_targets_workspace_bytes(shape)
     ws = _C.workspace(nws, dev)
-    _C.check(lib.cp_polydet_targets(
-        shape, _C.ptr(t["bbox"]), _C.ptr(t["poly"]), _C.ptr(t["cls_id"]), _C.ptr(t["pseudo_depth"]),
+    heatmap = _C.HEATMAP_ELLIPSE if elliptical_gt else _C.HEATMAP_UMICH
+    _C.check(lib.cp_polydet_targets_ex(
+        shape, heatmap, _C.ptr(t["bbox"]), _C.ptr(t["poly"]), _C.ptr(t["cls_id"]), _C.ptr(t["pseudo_depth"]),
         _C.ptr(t["freq"]), _C.ptr(t["num_objs"]), _C.ptr(t["flipped"]), _C.ptr(t["width"]),
         _C.ptr(t["trans_output"]), _C.ptr(out["hm"]), _C.ptr(out["border_hm"]), _C.ptr(out["reg_mask"]),
         _C.ptr(out["ind"]), _C.ptr(out["poly"]), _C.ptr(out["pseudo_depth"]), _C.ptr(out["peak"]),
         _C.ptr(out["reg"]), _C.ptr(out["wh"]), _C.ptr(out["freq_mask"]), _C.ptr(ws), nws, _C.stream()),
-        "cp_polydet_targets")
+        "cp_polydet_targets_ex")
     if not with_border_hm:
         del out["border_hm"]
     if cat_spec_poly:

@@ -14,6 +14,9 @@ class SyntheticPolydet(data.Dataset):
     max_objs = 128                                    # cityscapes.py:87
 
     def __init__(self, opt, split):
+        if getattr(opt, "elliptical_gt", False) and not getattr(opt, "device_targets", False):
+            raise ValueError("--elliptical_gt on the synthetic dataset needs --device_targets: its host targets "
+                             "(synth.train_batch) are UMich Gaussians only")
         self.opt = opt
         self.split = split
         self.num_samples = getattr(opt, "synthetic_samples", 64 if split == "train" else 8)

@@ -113,6 +113,9 @@ class opts(object):
         p.add_argument("--not_reg_offset", action="store_true")
         p.add_argument("--cat_spec_poly", action="store_true")
         p.add_argument("--dense_poly", action="store_true")
+        p.add_argument("--elliptical_gt", action="store_true",
+                       help="elliptical centre heat maps, stretched along the longer box side "
+                            "(draw_ellipse_gaussian); needs device-built targets")
         for flag in ("eval_oracle_hm", "eval_oracle_border_hm", "eval_oracle_offset",
                      "eval_oracle_poly", "eval_oracle_pseudo_depth"):
             p.add_argument("--" + flag, action="store_true")
@@ -120,6 +123,11 @@ class opts(object):
 
     def parse(self, args=""):
         opt = self.parser.parse_args() if args == "" else self.parser.parse_args(args)
+        if opt.elliptical_gt and opt.mse_loss:
+            # reference sample/polydet.py:201 replaces the radius by opt.hm_gauss under --mse_loss, an option its
+            # opts.py never defines: the combination has no target semantics to follow
+            self.parser.error("--elliptical_gt cannot be combined with --mse_loss: the reference sizes --mse_loss "
+                              "targets by --hm_gauss, which it never defines")
         opt.gpus_str = opt.gpus
         from . import arithmetic
         arithmetic.configure(opt.arithmetic)

@@ -116,7 +116,8 @@ class PolydetTrainer(BaseTrainer):
         targets = build_targets(batch, h, w, opt.num_classes, rep=opt.rep,
                                 no_reorder_flip=getattr(opt, "no_reorder_flip", False),
                                 with_border_hm=False, dense_poly=getattr(opt, "dense_poly", False),
-                                cat_spec_poly=getattr(opt, "cat_spec_poly", False))
+                                cat_spec_poly=getattr(opt, "cat_spec_poly", False),
+                                elliptical_gt=getattr(opt, "elliptical_gt", False))
         out = {k: v for k, v in batch.items() if k in ("input", "meta")}
         out.update(targets)
         return out

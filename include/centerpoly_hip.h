@@ -49,7 +49,8 @@ extern "C" {
 #endif
 
 #define CP_ABI_VERSION 3   /* 3 (round 4): + cp_polydet_decode_ex, cp_dense_l1_*, cp_polydet_dense_targets, cp_conv_direct_forward_ex,
-                              cp_conv_mfma_forward_split, cp_activation_split / _unsplit, cp_dla_base_pair_*; no signature changed */
+                              cp_conv_mfma_forward_split, cp_activation_split / _unsplit, cp_dla_base_pair_*; no signature changed.
+                              Added since, backward compatible (no version change): cp_polydet_targets_ex */
 
 enum {
   CP_OK = 0,
@@ -457,6 +458,32 @@ int cp_polydet_targets(const cp_target_shape* s, const double* bbox_xywh, const 
                        int64_t* ind, float* poly, float* pseudo_depth, float* peak, float* reg,
                        float* wh, float* freq_mask, void* workspace, size_t workspace_bytes,
                        void* stream);
+
+/* Centre heat map of cp_polydet_targets_ex (`--elliptical_gt`, src/lib/datasets/sample/polydet.py:156-159,223-228,
+ * src/lib/utils/image.py:144-173).
+ *   CP_HEATMAP_UMICH    draw_umich_gaussian: the (2r+1)^2 Gaussian, sigma = (2r+1)/6, values below DBL_EPSILON cut
+ *                       to 0.  What cp_polydet_targets draws (it is this mode of the same implementation).
+ *   CP_HEATMAP_ELLIPSE  draw_ellipse_gaussian into hm[class] with radius_x = r if h > w else int(r * (w / h)),
+ *                       radius_y = r if w >= h else int(r * (h / w)) (h, w: the float32 box sides after the affine
+ *                       and the clip; ratio and product in float32, then truncated).  Window (2ry+1) x (2rx+1) around
+ *                       the centre, clipped like the UMich one; at row offset dy, column offset dx the value is
+ *                       exp(-((dy*mr)^2 + (dx*mc)^2) / (2 sigma^2)) in float64 with mr = (2rx+1) / m,
+ *                       mc = (2ry+1) / m, m = max(2rx+1, 2ry+1), sigma = (2 min(rx, ry) + 1) / 6, no epsilon cut,
+ *                       max-composited into the float32 map.  border_hm keeps the UMich splats of radius r, and the
+ *                       ownership test of cp_polydet_dense_targets keeps the UMich Gaussian and window of radius r
+ *                       (draw_dense_reg), against the class maximum of the elliptical map.  Every other output is
+ *                       the UMich call's, bit for bit.
+ * The mode is recorded in the workspace, so cp_polydet_dense_targets follows it without an argument of its own. */
+enum { CP_HEATMAP_UMICH = 0, CP_HEATMAP_ELLIPSE = 1 };
+/* cp_polydet_targets with a centre heat map of `heatmap` (CP_HEATMAP_*; any other value: CP_EINVAL before any device
+ * work).  Same arguments, outputs and workspace as cp_polydet_targets. */
+int cp_polydet_targets_ex(const cp_target_shape* s, int32_t heatmap, const double* bbox_xywh, const double* poly_xy,
+                          const int32_t* cls_id, const float* pseudo_depth_in, const float* class_freq,
+                          const int32_t* num_objs, const uint8_t* flipped, const int32_t* img_width,
+                          const double* trans_output, float* hm, float* border_hm, uint8_t* reg_mask,
+                          int64_t* ind, float* poly, float* pseudo_depth, float* peak, float* reg,
+                          float* wh, float* freq_mask, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 /* `--dense_poly` targets (src/lib/datasets/sample/polydet.py:401-403,429-441 with draw_dense_reg,
  * src/lib/utils/image.py:176-204): after cp_polydet_targets on the SAME shape and workspace (its per-object
