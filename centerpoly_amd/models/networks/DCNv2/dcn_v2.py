@@ -17,7 +17,8 @@ import torch.nn as nn
 from torch.nn.modules.utils import _pair
 
 from .... import _C
-from ..conv3x3 import conv3x3_infer, conv_bias_act, conv_raw
+from ..conv3x3 import conv_bias_act, conv_infer, conv_raw
+from ..prepared import prepared
 
 
 def _shape(x, weight, stride, pad, dil, dg):
@@ -48,7 +49,7 @@ def dcn_v2_forward_raw(x, om, weight, bias, stride=1, pad=1, dil=1, dg=1, ep_sca
     """Forward on the raw offset/mask tensor `om` [B, 3*kh*kw, Ho, Wo] (mask as logits).
     Optional fused per-channel epilogue out = act(acc*ep_scale + ep_shift).
     `owner` (inference, contraction "bf16x3"): a module on which the workspace -- whose head holds the split,
-    permuted weights -- is kept for as long as `weight` is the same unmodified tensor and the shape the same, so
+    permuted weights -- is kept for as long as `weight` is the same tensor and the shapes the same (prepared.py), so
     that the permutation prologue runs once instead of per call."""
     L = _C.lib()
     s = _shape(x, weight, stride, pad, dil, dg)
@@ -63,15 +64,10 @@ def dcn_v2_forward_raw(x, om, weight, bias, stride=1, pad=1, dil=1, dg=1, ep_sca
     mode = _C.DCN_CONTRACTION[contraction]
     ws = None
     if owner is not None and mode in (1, 3):
-        # (data_ptr / device in the key: `module.to(device)` or a `.data` swap re-points the Parameter's storage without
-        # a version bump; a stale workspace would then hold another tensor's weights, possibly on another device)
-        key = (weight._version, weight.data_ptr(), str(weight.device), mode, tuple(x.shape), tuple(om.shape))
-        cache = owner.__dict__.get("_dcn_fwd_ws")
-        if cache is not None and cache[0] is weight and cache[1] == key:
-            ws, mode = cache[2], mode + 1                # CP_DCN_BF16X3[_REGION]_PREPARED
-        else:
-            ws = _C.workspace(nws, x.device)
-            owner.__dict__["_dcn_fwd_ws"] = (weight, key, ws)
+        ws, built = prepared(owner, "dcn_fwd", (weight,), lambda: _C.workspace(nws, x.device),
+                             (mode, tuple(x.shape), tuple(om.shape)))
+        if not built:
+            mode += 1                                    # CP_DCN_BF16X3[_REGION]_PREPARED
     elif nws:
         ws = _C.workspace(nws, x.device)
     timer = _C.kernel_timer
@@ -96,24 +92,15 @@ def dcn_v2_module_forward(x, om_weight, om_bias, weight, bias, ep_scale=None, ep
             or not L.cp_dcn_v2_forward_fused_supported(s):
         return None
     nws = L.cp_dcn_v2_forward_fused_workspace_bytes(s)
-    prepared, ws = 0, None
-    if owner is not None:
-        key = (weight._version, weight.data_ptr(), om_weight._version, om_weight.data_ptr(), str(weight.device), tuple(x.shape))
-        cache = owner.__dict__.get("_dcn_fused_ws")
-        if cache is not None and cache[0] is weight and cache[1] is om_weight and cache[2] == key:
-            ws, prepared = cache[3], 1
-        else:
-            ws = _C.workspace(nws, x.device)
-            owner.__dict__["_dcn_fused_ws"] = (weight, om_weight, key, ws)
-    else:
-        ws = _C.workspace(nws, x.device)
+    ws, built = (_C.workspace(nws, x.device), True) if owner is None else \
+        prepared(owner, "dcn_fused", (weight, om_weight), lambda: _C.workspace(nws, x.device), tuple(x.shape))
     out = torch.empty((s.B, s.Cout, s.H, s.W), dtype=torch.float32, device=x.device)
     om = torch.empty((s.B, 27, s.H, s.W), dtype=torch.float32, device=x.device) if want_om else None
     timer = _C.kernel_timer
     end = timer.start(("dcn_fwd", s.Cin, s.Cout, s.H, s.W, s.B)) if timer is not None else None
     rc = L.cp_dcn_v2_forward_fused(s, _C.ptr(x), _C.ptr(om_weight), _C.ptr(om_bias), _C.ptr(weight), _C.ptr(bias),
-                                   _C.ptr(ep_scale), _C.ptr(ep_shift), 1 if relu else 0, prepared, _C.ptr(om), _C.ptr(out),
-                                   _C.ptr(ws), nws, _C.stream())
+                                   _C.ptr(ep_scale), _C.ptr(ep_shift), 1 if relu else 0, 0 if built else 1, _C.ptr(om),
+                                   _C.ptr(out), _C.ptr(ws), nws, _C.stream())
     if end is not None:
         end.record()
     _C.check(rc, "cp_dcn_v2_forward_fused")
@@ -350,7 +337,7 @@ class DCN(nn.Module):
                                       owner=self)
             if r is not None:
                 return r[0]
-        om = conv3x3_infer(x, cm, cm.weight, cm.bias, conv=cm)      # split-bf16 MFMA kernel, bias in its epilogue
+        om = conv_infer([x], cm, cm.weight, cm.bias, conv=cm)       # split-bf16 MFMA kernel, bias in its epilogue
         if om is None:
             om = cm(x)
         return dcn_v2_forward_raw(x.contiguous(), om.contiguous(), self.weight, None, self.stride,

@@ -6,7 +6,7 @@ to cuDNN.  float32 in and out; forward and input gradient run on the bf16 matrix
 products of split halves, and so does the weight gradient (cp_conv3x3_mfma_wgrad).
 
 `conv_raw(conv, x)` is what every training call site uses for "conv without its bias";
-`conv3x3_infer(x, conv, w, bias, residual, relu)` is the inference call with the fused epilogue.
+`conv_infer([x], conv, w, bias, residual, relu)` is the inference call with the fused epilogue.
 Shapes the kernel does not take (stride 2, 1x1, 7x7, fewer than 24 input channels, tiny maps) go to the direct
 kernel or the library.  `centerpoly_amd.arithmetic.configure("exact_f32")` turns the kernels off (library fp32)."""
 
@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from ... import _C
+from .prepared import prepared
 
 _ENABLED = True              # set by centerpoly_amd.arithmetic.configure
 _WGRAD = True
@@ -144,8 +145,11 @@ def _prepare(weight, cin, cout, transposed):
     kernel's mode code (6: the one-launch stride-2 input gradient)."""
     code = int(transposed) if not isinstance(transposed, bool) else (1 if transposed else 0)
     wp = _BANK.get(weight, cin, cout, code)
-    if wp is not None:
-        return wp
+    return wp if wp is not None else _permute(weight, cin, cout, code)
+
+
+def _permute(weight, cin, cout, code):
+    """One launch of cp_conv_mfma_prepare into a fresh buffer (see _prepare for `code`)."""
     L = _C.lib()
     taps = weight.shape[2] * weight.shape[3]
     wp = torch.empty(L.cp_conv_mfma_weight_bytes(cin, cout, taps), dtype=torch.uint8, device=weight.device)
@@ -167,11 +171,11 @@ def _launch(x, wp, bias, residual, cout, relu, taps=9, stride=1):
     return out
 
 
-def conv_infer(xs, owner, w, bias=None, residual=None, relu=False, conv=None, key="_mfma_wperm", x_split=False,
+def conv_infer(xs, owner, w, bias=None, residual=None, relu=False, conv=None, slot="conv", x_split=False,
                out_split=False):
     """Inference: 3x3 / pad 1 or 1x1 (stride 1 or 2) convolution of the channel concatenation of `xs` -- read in place,
     no torch.cat -- with the (folded) weight `w`, + bias + residual + ReLU in the kernel's epilogue.  The permuted
-    weights are cached on `owner` (under `key`) for as long as `w` is the same, unmodified tensor.  `conv`, when
+    weights are kept on `owner` (under `slot`, see prepared.py) for as long as `w` is the same tensor.  `conv`, when
     given, is the module whose geometry must be the kernel's.  Returns None when the shape is not the kernel's.
     x_split / out_split (one source, 3x3): the input / output is a SPLIT tensor -- the [hi | lo] bf16 planes of
     cp_conv_mfma_forward_split held in a float32 tensor of the logical shape (same bytes; only such a convolution may
@@ -202,13 +206,7 @@ def conv_infer(xs, owner, w, bias=None, residual=None, relu=False, conv=None, ke
             or not _fills(B, cin, cout, Ho, Wo) or (residual is not None and not residual.is_contiguous()):
         return None
     taps = k[0] * k[1]
-    cache = owner.__dict__.get(key)
-    if cache is None or cache[0] is not w or cache[1] != w._version:
-        wp = torch.empty(L.cp_conv_mfma_weight_bytes(cin, cout, taps), dtype=torch.uint8, device=w.device)
-        _C.check(L.cp_conv_mfma_prepare(_C.ptr(w.contiguous()), cin, cout, taps, 0, _C.ptr(wp), _C.stream()),
-                 "cp_conv_mfma_prepare")
-        cache = (w, w._version, wp)
-        owner.__dict__[key] = cache
+    wp, _ = prepared(owner, slot, (w,), lambda: _permute(w.contiguous(), cin, cout, 0))
     xs = [x.contiguous() for x in xs]
     out = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x0.device)
     ptrs = (_C.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
@@ -218,11 +216,11 @@ def conv_infer(xs, owner, w, bias=None, residual=None, relu=False, conv=None, ke
     if x_split or out_split:
         if x_split and stride != 1:
             return None
-        _C.check(L.cp_conv_mfma_forward_split(_C.ptr(xs[0]), 1 if x_split else 0, _C.ptr(cache[2]), _C.ptr(bias),
+        _C.check(L.cp_conv_mfma_forward_split(_C.ptr(xs[0]), 1 if x_split else 0, _C.ptr(wp), _C.ptr(bias),
                                               _C.ptr(residual), _C.ptr(out), 1 if out_split else 0, B, cin, H, W, cout,
                                               taps, stride, 1 if relu else 0, _C.stream()), "cp_conv_mfma_forward_split")
     else:
-        _C.check(L.cp_conv_mfma_forward_strided(ptrs, chans, len(xs), _C.ptr(cache[2]), _C.ptr(bias), _C.ptr(residual),
+        _C.check(L.cp_conv_mfma_forward_strided(ptrs, chans, len(xs), _C.ptr(wp), _C.ptr(bias), _C.ptr(residual),
                                                 _C.ptr(out), B, H, W, cout, taps, stride, 1 if relu else 0, _C.stream()),
                  "cp_conv_mfma_forward_strided")
     if end is not None:
@@ -254,11 +252,6 @@ def block_infer(x, conv1, wb1, conv2, wb2, skip):
     return z
 
 
-def conv3x3_infer(x, owner, w, bias=None, residual=None, relu=False, conv=None, key="_mfma_wperm"):
-    """conv_infer for one input tensor (kept for the call sites that predate the 1x1 / multi-source form)."""
-    return conv_infer([x], owner, w, bias, residual, relu, conv=conv, key=key)
-
-
 def s2_input_grad(xshape, weight, go):
     """Input gradient of a 3x3 / stride 2 / pad 1 convolution: one launch of the MFMA convolution over grad_out with
     the four parity classes' accumulators (cp_conv3x3_s2_input_grad); None where the kernel does not take the shape."""
@@ -284,7 +277,7 @@ def s2_input_grad(xshape, weight, go):
 def stem_infer(x, conv, w, bias, relu):
     """Inference: a 7x7 / pad 3 convolution of a 3-channel image, stride 1 (DLA's base_layer) or 2 (the Hourglass stem),
     on the bf16 matrix cores (cp_conv7x7_c3_forward) with the (folded) weight `w`, + bias + ReLU in the epilogue; the
-    permuted weights are cached on `conv` for as long as `w` is the same, unmodified tensor.  None when the module is
+    permuted weights are kept on `conv` for as long as `w` is the same tensor (prepared.py).  None when the module is
     not that convolution (or the arithmetic is exact_f32)."""
     if not (_ENABLED and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and conv.kernel_size == (7, 7)
             and conv.stride in ((1, 1), (2, 2)) and conv.padding == (3, 3) and conv.dilation == (1, 1) and conv.groups == 1
@@ -295,14 +288,14 @@ def stem_infer(x, conv, w, bias, relu):
     cout, stride = w.shape[0], conv.stride[0]
     if not L.cp_conv7x7_c3_supported(cout, H, W, stride) or B > 65535:
         return None
-    cache = conv.__dict__.get("_stem_wperm")
-    if cache is None or cache[0] is not w or cache[1] != w._version:
+
+    def build():
         wp = torch.empty(L.cp_conv7x7_c3_weight_bytes(cout), dtype=torch.uint8, device=w.device)
         _C.check(L.cp_conv7x7_c3_prepare(_C.ptr(w.contiguous()), cout, _C.ptr(wp), _C.stream()), "cp_conv7x7_c3_prepare")
-        cache = (w, w._version, wp)
-        conv.__dict__["_stem_wperm"] = cache
+        return wp
+    wp, _ = prepared(conv, "stem", (w,), build)
     out = torch.empty((B, cout, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=torch.float32, device=x.device)
-    _C.check(L.cp_conv7x7_c3_forward(_C.ptr(x.contiguous()), _C.ptr(cache[2]), _C.ptr(bias), _C.ptr(out), B, H, W, cout,
+    _C.check(L.cp_conv7x7_c3_forward(_C.ptr(x.contiguous()), _C.ptr(wp), _C.ptr(bias), _C.ptr(out), B, H, W, cout,
                                      stride, 1 if relu else 0, _C.stream()), "cp_conv7x7_c3_forward")
     return out
 

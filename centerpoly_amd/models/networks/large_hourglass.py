@@ -15,8 +15,9 @@ import torch.nn.functional as F
 
 from ... import _C
 from . import conv3x3
-from .conv3x3 import conv3x3_infer
-from .pose_dla_dcn import _conv_folded, _fold_conv_bn, _use_folded, bn_act, conv_train, flush_batch_counts, heads_fused_infer
+from .pose_dla_dcn import (_conv_folded, _fold_conv_bn, _use_folded, bn_act, cat_heads, conv_train, flush_batch_counts,
+                           heads_infer)
+from .prepared import release_inference
 
 # Inference (`prepare_inference()`): every BatchNorm is folded into its convolution (weights scaled,
 # shift as a bias) and each conv is followed by ONE fused in-place pass -- + bias (+ residual) (+ ReLU),
@@ -196,60 +197,15 @@ class exkp(nn.Module):
         with torch.no_grad():
             self._inter_folded = [(_fold_conv_bn(a[0], a[1]), _fold_conv_bn(b[0], b[1]))
                                   for a, b in zip(self.inters_, self.cnvs_)]
-            self._heads_cat = []
-            for s in range(self.nstack):
-                fcs = [getattr(self, h)[s] for h in self.heads]
-                w = torch.cat([fc[0].conv.weight for fc in fcs], 0).contiguous()
-                b = torch.cat([fc[0].conv.bias for fc in fcs], 0).contiguous()
-                tails = [(fc[1].weight.reshape(fc[1].out_channels, -1).t().contiguous(),
-                          fc[1].bias.detach().clone(), fc[0].conv.out_channels, fc[1].out_channels) for fc in fcs]
-                self._heads_cat.append((w, b, tails))
+        heads = [getattr(self, h) for h in self.heads]
+        self._heads_cat = [cat_heads([(fc[s][0].conv, fc[s][1]) for fc in heads]) for s in range(self.nstack)]
         return self
 
     def train(self, mode=True):
         if mode:
-            for m in self.modules():
-                if hasattr(m, "_folded"):
-                    m._folded = None
-                for k in [k for k in m.__dict__ if k.startswith(("_mfma_wperm", "_heads_wperm", "_stem_wperm", "_dcn_fwd_ws", "_dcn_fused_ws"))]:
-                    del m.__dict__[k]          # permuted inference weights / DCN workspaces of the folded tensors
-            self._heads_cat = None
-            self._inter_folded = None
+            release_inference(self)            # folded weights, heads' concatenations, prepared forms
         _C.release_zero_pool()                 # (gradient accumulators of the mode being left)
         return super().train(mode)
-
-    def _heads_fast(self, s, cnv):
-        w, b, tails = self._heads_cat[s]
-        out = heads_fused_infer(self, "_heads_fused_cache%d" % s, cnv, w, b, tails, list(self.heads))
-        if out is not None:
-            return out
-        y = conv3x3_infer(cnv, self, w, key="_heads_wperm%d" % s)
-        if y is None:
-            y = F.conv2d(cnv, w, None, padding=1)
-        B, ctot, H, W = y.shape
-        hw = H * W
-        out, c0 = {}, 0
-        L = _C.lib()
-        for h, (w_t, b1, hc, co) in zip(self.heads, tails):
-            o = torch.empty((B, co, H, W), dtype=torch.float32, device=y.device)
-            if co <= 32:
-                _C.check(L.cp_conv1x1_act_forward(
-                    _C.c_void_p(y.data_ptr() + 4 * c0 * hw), ctot * hw, _C.c_void_p(b.data_ptr() + 4 * c0), 1,
-                    _C.ptr(w_t), _C.ptr(b1), _C.ptr(o), B, hc, co, hw, _C.stream()), "cp_conv1x1_act_forward")
-            else:                                   # wide head (48-channel polar polygons): 32-channel slices
-                for a0 in range(0, co, 32):
-                    a1 = min(co, a0 + 32)
-                    wt = w_t[:, a0:a1].contiguous()
-                    bb = b1[a0:a1].contiguous()
-                    for i in range(B):
-                        _C.check(L.cp_conv1x1_act_forward(
-                            _C.c_void_p(y.data_ptr() + 4 * (i * ctot + c0) * hw), ctot * hw,
-                            _C.c_void_p(b.data_ptr() + 4 * c0), 1, _C.ptr(wt), _C.ptr(bb),
-                            _C.c_void_p(o.data_ptr() + 4 * (i * co + a0) * hw), 1, hc, a1 - a0, hw, _C.stream()),
-                            "cp_conv1x1_act_forward")
-            out[h] = o
-            c0 += hc
-        return out
 
     def forward(self, image):
         try:
@@ -260,7 +216,7 @@ class exkp(nn.Module):
             for s in range(self.nstack):
                 cnv = self.cnvs[s](self.kps[s](inter))
                 if fused and (cnv.shape[2] * cnv.shape[3]) % 4 == 0:
-                    outs.append(self._heads_fast(s, cnv))
+                    outs.append(heads_infer(self, s, cnv, self._heads_cat[s], list(self.heads)))
                 else:
                     outs.append({head: getattr(self, head)[s](cnv) for head in self.heads})
                 if s < self.nstack - 1:

@@ -21,7 +21,8 @@ from torch import nn
 from ... import _C
 from .DCNv2.dcn_v2 import DCN, conv_bias
 from . import conv3x3
-from .conv3x3 import conv3x3_infer, conv_infer, conv_raw
+from .conv3x3 import conv_infer, conv_raw
+from .prepared import prepared, release_inference
 
 # A/B switches of this module (tools/probe_*.py set them; nothing reads the environment)
 HEADS_FUSED = True           # all heads of a stage as one kernel (cp_heads_fused_forward)
@@ -185,7 +186,7 @@ def _conv_folded(x, conv, wb, relu=False, residual=None):
         if y is not None:
             return y
     if x.is_cuda:
-        y = conv3x3_infer(x, conv, wb[0], wb[1], residual, relu, conv=conv)
+        y = conv_infer([x], conv, wb[0], wb[1], residual, relu, conv=conv)
         if y is not None:
             return y
     if not x.is_cuda:
@@ -687,11 +688,23 @@ class DLAUp(nn.Module):
         return out
 
 
-def heads_fused_infer(owner, key, feat, w, b, tails, names):
+def cat_heads(pairs):
+    """(w, b, tails) of heads Conv2d(3x3, bias) -> ReLU -> Conv2d(1x1) over one feature map, from their (3x3, 1x1)
+    convolutions: w, b the 3x3 weights / biases concatenated along the output channels; tails per head (1x1 weight
+    transposed [hc][co], 1x1 bias or None, hc, co)."""
+    with torch.no_grad():
+        w = torch.cat([c3.weight for c3, _ in pairs], 0).contiguous()
+        b = torch.cat([c3.bias for c3, _ in pairs], 0).contiguous()
+        tails = [(c1.weight.reshape(c1.out_channels, -1).t().contiguous(),
+                  c1.bias.detach().clone() if c1.bias is not None else None, c3.out_channels, c1.out_channels)
+                 for c3, c1 in pairs]
+    return w, b, tails
+
+
+def heads_fused_infer(owner, stage, feat, w, b, tails, names):
     """All heads of one output stage as ONE kernel (cp_heads_fused_forward): 3x3 convolution + bias + ReLU + 1x1
     convolution + bias, the nheads x head_conv-channel intermediate never leaves the accumulator registers.
-    w, b: the heads' 3x3 weights / biases concatenated along the output channels; tails: per head (1x1 weight
-    transposed [hc][co], 1x1 bias or None, hc, co).  The permuted weights are cached on `owner` under `key`.
+    w, b, tails: see cat_heads.  The permuted weights are kept on `owner` per `stage` (prepared.py).
     None when the shapes are not the kernel's (more than 4 heads, a head wider than 64 outputs, head_conv not a
     multiple of 64, input channels not a multiple of 32)."""
     if not HEADS_FUSED or not conv3x3.mfma_enabled():
@@ -705,8 +718,8 @@ def heads_fused_infer(owner, key, feat, w, b, tails, names):
     if hc % 64 != 0:
         return None
     L = _C.lib()
-    cache = owner.__dict__.get(key)
-    if cache is None or cache[0] is not w or cache[1] != w._version:
+
+    def build():
         wp1 = conv3x3._prepare(w, cin, w.shape[0], False)
         w2p = []
         for (w_t, b2, _, co) in tails:
@@ -715,19 +728,19 @@ def heads_fused_infer(owner, key, feat, w, b, tails, names):
             _C.check(L.cp_heads_fused_prepare_w2(_C.ptr(w2), co, hc, _C.ptr(buf), _C.stream()),
                      "cp_heads_fused_prepare_w2")
             w2p.append(buf)
-        cache = (w, w._version, wp1, w2p)
-        owner.__dict__[key] = cache
+        return wp1, w2p
+    (wp1, w2p), _ = prepared(owner, ("heads_fused", stage), (w,) + tuple(t[0] for t in tails), build)
     feat = feat.contiguous()
     outs = [torch.empty((B, t[3], H, W), dtype=torch.float32, device=feat.device) for t in tails]
     n = len(tails)
     vp = _C.c_void_p
-    w2arr = (vp * n)(*[t.data_ptr() for t in cache[3]])
+    w2arr = (vp * n)(*[t.data_ptr() for t in w2p])
     b2arr = (vp * n)(*[(t[1].data_ptr() if t[1] is not None else None) for t in tails])
     oarr = (vp * n)(*[o.data_ptr() for o in outs])
     carr = (_C.c_int32 * n)(*[t[3] for t in tails])
     end = _C.kernel_timer.start(("heads_fused", cin, w.shape[0], H, W, B, hc, sum(t[3] for t in tails))) \
         if _C.kernel_timer is not None else None
-    rc = L.cp_heads_fused_forward(_C.ptr(feat), _C.ptr(cache[2]), _C.ptr(b), w2arr, b2arr, oarr, carr, n, B, cin, H, W,
+    rc = L.cp_heads_fused_forward(_C.ptr(feat), _C.ptr(wp1), _C.ptr(b), w2arr, b2arr, oarr, carr, n, B, cin, H, W,
                                   hc, _C.stream())
     if end is not None:
         end.record()
@@ -735,6 +748,45 @@ def heads_fused_infer(owner, key, feat, w, b, tails, names):
         return None
     _C.check(rc, "cp_heads_fused_forward")
     return dict(zip(names, outs))
+
+
+def heads_infer(owner, stage, feat, cat, names):
+    """{name: head(feat)} of one output stage at inference from the heads' concatenation `cat` (cat_heads): the fused
+    heads kernel where it takes the shapes; else all heads' 3x3 convolutions as ONE convolution (they share the input)
+    and each head's bias + ReLU + 1x1 convolution as one streaming kernel over its channel slice of the raw result
+    (cp_conv1x1_act_forward) -- the concatenated map is read once instead of going through a bias/ReLU pass and a
+    GEMM with a handful of output rows.  The prepared weights are kept on `owner` per `stage`."""
+    w, b, tails = cat
+    out = heads_fused_infer(owner, stage, feat, w, b, tails, names)
+    if out is not None:
+        return out
+    y = conv_infer([feat], owner, w, slot=("heads_conv", stage))
+    if y is None:
+        y = F.conv2d(feat, w, None, padding=1)
+    B, ctot, H, W = y.shape
+    hw = H * W
+    out, c0 = {}, 0
+    L = _C.lib()
+    for h, (w_t, b1, hc, co) in zip(names, tails):
+        o = torch.empty((B, co, H, W), dtype=torch.float32, device=y.device)
+        if co <= 32:
+            _C.check(L.cp_conv1x1_act_forward(
+                _C.c_void_p(y.data_ptr() + 4 * c0 * hw), ctot * hw, _C.c_void_p(b.data_ptr() + 4 * c0), 1,
+                _C.ptr(w_t), _C.ptr(b1), _C.ptr(o), B, hc, co, hw, _C.stream()), "cp_conv1x1_act_forward")
+        else:                                   # wide head (48-channel polar polygons): 32-channel slices
+            for a0 in range(0, co, 32):
+                a1 = min(co, a0 + 32)
+                wt = w_t[:, a0:a1].contiguous()
+                bb = b1[a0:a1].contiguous() if b1 is not None else None
+                for i in range(B):
+                    _C.check(L.cp_conv1x1_act_forward(
+                        _C.c_void_p(y.data_ptr() + 4 * (i * ctot + c0) * hw), ctot * hw,
+                        _C.c_void_p(b.data_ptr() + 4 * c0), 1, _C.ptr(wt), _C.ptr(bb),
+                        _C.c_void_p(o.data_ptr() + 4 * (i * co + a0) * hw), 1, hc, a1 - a0, hw, _C.stream()),
+                        "cp_conv1x1_act_forward")
+        out[h] = o
+        c0 += hc
+    return out
 
 
 class DLASeg(nn.Module):
@@ -785,55 +837,14 @@ class DLASeg(nn.Module):
                 m.contraction = None if dcn_contraction == "auto" else dcn_contraction   # None: DCN.infer_contraction
         self._heads_cat = None
         fcs = [getattr(self, h) for h in self.heads]
-        if all(isinstance(fc, nn.Sequential) and len(fc) == 3 for fc in fcs):
-            with torch.no_grad():
-                tails = [(fc[2].weight.reshape(fc[2].out_channels, -1).t().contiguous(),
-                          fc[2].bias.detach().clone() if fc[2].bias is not None else None,
-                          fc[0].out_channels, fc[2].out_channels) for fc in fcs]
-                fast = all(fc[2].kernel_size == (1, 1) and fc[2].out_channels <= 32 and fc[0].bias is not None
-                           and fc[0].kernel_size == (3, 3) for fc in fcs)
-                if fast:
-                    self._heads_cat = (torch.cat([fc[0].weight for fc in fcs], 0).contiguous(),
-                                       torch.cat([fc[0].bias for fc in fcs], 0).contiguous(), tails)
+        if all(isinstance(fc, nn.Sequential) and len(fc) == 3 and fc[2].kernel_size == (1, 1)
+               and fc[2].out_channels <= 32 and fc[0].bias is not None and fc[0].kernel_size == (3, 3) for fc in fcs):
+            self._heads_cat = cat_heads([(fc[0], fc[2]) for fc in fcs])
         return self
-
-    def _heads_fused(self, feat):
-        w, b, tails = self._heads_cat
-        return heads_fused_infer(self, "_heads_fused_cache", feat, w, b, tails, list(self.heads))
-
-    def _heads_fast(self, feat):
-        """All heads' conv3x3 as ONE library convolution (they share the input); each head's
-        bias + ReLU + 1x1 convolution is then one streaming kernel over its channel slice of the
-        raw result (cp_conv1x1_act_forward) -- the 4x256-channel tensor is read once instead of
-        going through a bias/ReLU pass and a GEMM with a handful of output rows."""
-        w, b, tails = self._heads_cat
-        out = self._heads_fused(feat)
-        if out is not None:
-            return out
-        y = conv3x3_infer(feat, self, w, key="_heads_wperm")
-        if y is None:
-            y = F.conv2d(feat, w, None, padding=1)
-        B, ctot, H, W = y.shape
-        hw = H * W
-        out, c0 = {}, 0
-        L = _C.lib()
-        for h, (w_t, b1, hc, co) in zip(self.heads, tails):
-            o = torch.empty((B, co, H, W), dtype=torch.float32, device=y.device)
-            _C.check(L.cp_conv1x1_act_forward(
-                _C.c_void_p(y.data_ptr() + 4 * c0 * hw), ctot * hw, _C.c_void_p(b.data_ptr() + 4 * c0), 1,
-                _C.ptr(w_t), _C.ptr(b1), _C.ptr(o), B, hc, co, hw, _C.stream()), "cp_conv1x1_act_forward")
-            out[h] = o
-            c0 += hc
-        return out
 
     def train(self, mode=True):
         if mode:
-            for m in self.modules():
-                if hasattr(m, "_folded"):
-                    m._folded = None
-                for k in [k for k in m.__dict__ if k.startswith(("_mfma_wperm", "_heads_wperm", "_heads_fused", "_dcn_fwd_ws", "_dcn_fused_ws", "_stem_wperm"))]:
-                    del m.__dict__[k]          # permuted inference weights / DCN workspaces of the folded tensors
-            self._heads_cat = None
+            release_inference(self)            # folded weights, heads' concatenation, prepared forms
         _C.release_zero_pool()                 # (gradient accumulators of the mode being left)
         return super().train(mode)
 
@@ -853,7 +864,7 @@ class DLASeg(nn.Module):
         if getattr(self, "_heads_cat", None) is not None and not self.training \
                 and not torch.is_grad_enabled() and y[-1].is_cuda \
                 and (y[-1].shape[2] * y[-1].shape[3]) % 4 == 0:
-            return [self._heads_fast(y[-1])]
+            return [heads_infer(self, 0, y[-1], self._heads_cat, list(self.heads))]
         if self.training and y[-1].is_cuda and all(
                 isinstance(getattr(self, h), nn.Sequential) and len(getattr(self, h)) == 3 for h in self.heads):
             # training: each head's Conv3x3 + bias + ReLU with the fused epilogue, then its 1x1 conv

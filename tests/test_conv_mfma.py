@@ -703,14 +703,35 @@ def test_residual_blocks_with_split_intermediate_equal_the_float32_route(case):
     with torch.no_grad():
         z = conv3x3.block_infer(x, blk.conv1, f1, blk.conv2, f2, skip)
         assert z is not None                                   # the split route ran
-        y = conv3x3.conv3x3_infer(x, blk.conv1, f1[0], f1[1], None, True, conv=blk.conv1)
-        ref = conv3x3.conv3x3_infer(y, blk.conv2, f2[0], f2[1], skip, True, conv=blk.conv2)
+        y = conv3x3.conv_infer([x], blk.conv1, f1[0], f1[1], None, True, conv=blk.conv1)
+        ref = conv3x3.conv_infer([y], blk.conv2, f2[0], f2[1], skip, True, conv=blk.conv2)
         assert torch.equal(z, ref)
         lin = F.relu(F.conv2d(x.double(), f1[0].double(), f1[1].double(), stride=stride, padding=1))
         full = F.relu(F.conv2d(lin, f2[0].double(), f2[1].double(), padding=1) + skip.double())
         assert _rel(z, full) <= 2 * TOL                        # two chained contractions
         if kind == "dla":
             assert torch.equal(blk(x, skip), ref)              # the module takes the same route
+
+
+@pytest.mark.parametrize("k,cin,cout,stride", [(3, 64, 64, 1), (7, 3, 128, 2)], ids=["conv_infer", "stem_infer"])
+def test_prepared_weights_follow_a_repointed_parameter(k, cin, cout, stride):
+    """Hourglass convolution(with_bn=False) folds to its Parameters themselves: a `.data` swap after fold() points the
+    weight at new storage without a version bump, and the next inference call must run with the new weights, not with
+    the permuted form prepared from the old ones (3x3: the MFMA convolution; 7x7 / 3 channels: the stem kernel)."""
+    from centerpoly_amd.models.networks import large_hourglass
+    torch.manual_seed(4)
+    m = large_hourglass.convolution(k, cin, cout, stride=stride, with_bn=False).to(DEV).eval()
+    m.fold()
+    x = _t("repoint/x%d" % k, (1, cin, 64, 128))
+    new = _t("repoint/w%d" % k, tuple(m.conv.weight.shape), 0.05)
+    keys = set(m.conv.__dict__)
+    with torch.no_grad():
+        m(x)
+        assert set(m.conv.__dict__) != keys                # the kernel route ran: it kept a prepared form on the conv
+        m.conv.weight.data = new
+        out = m(x)
+    ref = F.relu(F.conv2d(x.double(), new.double(), m.conv.bias.double(), stride=stride, padding=k // 2))
+    assert _rel(out, ref) <= TOL
 
 
 # ---- level0 + level1 of the DLA base in one launch (csrc/conv_base_pair.hip) -------------------------------------------

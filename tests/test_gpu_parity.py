@@ -913,6 +913,17 @@ def test_folded_conv_epilogue_matches_bn_relu():
 
 # ------------------------------------------------------------------- nets ---
 
+def _inference_state(model):
+    """(module, attribute) pairs through which `model` still holds a tensor outside its parameters and buffers: folded
+    weights, concatenated heads, prepared forms."""
+    def holds(v):
+        if isinstance(v, dict):
+            v = list(v.values())
+        return isinstance(v, torch.Tensor) or (isinstance(v, (tuple, list)) and any(holds(u) for u in v))
+    return [(name, k) for name, q in model.named_modules() for k, v in vars(q).items()
+            if k not in ("_parameters", "_buffers") and holds(v)]
+
+
 def _load_by_name(model, gold):
     shapes = {k: tuple(v) for k, v in json.loads(str(gold["shapes"])).items()}
     model.load_state_dict({k: T(v) for k, v in cases.fill_weights(shapes).items()})
@@ -936,6 +947,9 @@ def test_dla34_forward_vs_reference_golden(fused, golden):
     for h in dict(cases.HEADS):
         ref = gold["s0_" + h]
         np.testing.assert_allclose(out[h].cpu().numpy(), ref, rtol=1e-3, atol=1e-4 * np.abs(ref).max())
+    if fused:
+        m.train()
+        assert not _inference_state(m)
 
 
 @pytest.mark.parametrize("shape", [(2, 5, 6, 8), (1, 3, 7, 9), (1, 256, 16, 32)], ids=["even", "odd", "wide"])
@@ -1242,6 +1256,7 @@ def test_hourglass_prepare_inference_matches_plain_eval(ns, poly, hw):
             assert (a[h] - b[h]).abs().max().item() <= 2e-4 * scale, h
     m.train()
     assert m._heads_cat is None and all(getattr(q, "_folded", None) is None for q in m.modules())
+    assert not _inference_state(m)
 
 
 def test_direct_conv_training_function_gradients():
