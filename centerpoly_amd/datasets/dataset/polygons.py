@@ -131,19 +131,20 @@ class CityscapesWriterMixin(object):
                     params.append((pts, row[4], self.class_name[cls_ind], row[-1]))
         return sorted(params, key=lambda a: a[-1])
 
-    def instance_masks(self, params, device=None):
-        """Occlusion-ordered masks of depth-sorted instances: (uint8 [n, H, W] host array, counts [n])."""
+    def instance_masks_device(self, params, device=None):
+        """Occlusion-ordered masks of depth-sorted instances, left on the device:
+        (uint8 [n, H, W] tensor, int32 [n] tensor of pixel counts)."""
         import torch
 
         from ... import _C
         W, H = self.canvas
         n = len(params)
-        if n == 0:
-            return np.zeros((0, H, W), np.uint8), np.zeros((0,), np.int32)
+        if n == 0:                                           # nothing to draw: no device needed (or touched)
+            return torch.zeros((0, H, W), dtype=torch.uint8), torch.zeros((0,), dtype=torch.int32)
+        dev = device or torch.device("cuda")
         if n > 128:
             raise ValueError("more than 128 instances in one image (max_per_image = K <= 128)")
         N = len(params[0][0])
-        dev = device or torch.device("cuda")
         poly = torch.tensor([p[0] for p in params], dtype=torch.int32).reshape(n, N, 2).to(dev)
         flags = torch.tensor([(0 if p[2] in self.no_mask_labels else 1) | (2 if p[1] >= 0.5 else 0) for p in params],
                              dtype=torch.uint8).to(dev)
@@ -151,26 +152,50 @@ class CityscapesWriterMixin(object):
         counts = torch.empty((n,), dtype=torch.int32, device=dev)
         _C.check(_C.lib().cp_instance_masks(_C.ptr(poly), _C.ptr(flags), n, N, H, W, _C.ptr(masks), _C.ptr(counts),
                                             _C.stream()), "cp_instance_masks")
+        return masks, counts
+
+    def instance_masks(self, params, device=None):
+        """Occlusion-ordered masks of depth-sorted instances: (uint8 [n, H, W] host array, counts [n])."""
+        masks, counts = self.instance_masks_device(params, device)
         return masks.cpu().numpy(), counts.cpu().numpy()
 
-    def format_and_write_to_cityscapes(self, all_bboxes, save_dir):
+    def format_and_write_to_cityscapes(self, all_bboxes, save_dir, evaluator=None, gt_files=None, write_files=True):
+        """Writes the result files; with an `evaluator` (evaluation.instance_level.InstanceLevelEvaluator) the kept
+        masks are also scored against `gt_files` ({image prefix: id image path}) while they are on the device."""
         from PIL import Image
         id_to_file = {im["id"]: im["file_name"] for im in self.coco.imgs.values()}
         masks_dir = os.path.join(save_dir, "masks")
-        os.makedirs(masks_dir, exist_ok=True)
+        if write_files:
+            os.makedirs(masks_dir, exist_ok=True)
         for image_id in all_bboxes:
             base = os.path.basename(id_to_file[int(image_id)])
             params = self.image_instances(all_bboxes[image_id])
-            masks, counts = self.instance_masks(params)
-            count = 0
+            masks_dev, counts_dev = self.instance_masks_device(params)
+            counts = counts_dev.cpu().numpy()
+            # the writer's selection: labels with masks, more than 100 pixels; the confidence is the text line's
+            kept = [k for k, (p, nz) in enumerate(zip(params, counts)) if p[2] not in self.no_mask_labels and nz > 100]
+            confs = [str(min(1, params[k][1] * 1.2)) for k in kept]
+            if evaluator is not None:
+                from ..evaluation import instance_level
+                prefix = base[:-len("_leftImg8bit.png")] if base.endswith("_leftImg8bit.png") else os.path.splitext(base)[0]
+                if prefix not in gt_files:
+                    raise FileNotFoundError("no ground truth %s%s below --gt_dir for image %s"
+                                            % (prefix, instance_level.GT_SUFFIX, base))
+                gt_ids = instance_level.read_gt_ids(gt_files[prefix])
+                if gt_ids.shape != tuple(masks_dev.shape[1:]):
+                    raise ValueError("%s is %s, the result canvas is %s" % (gt_files[prefix], gt_ids.shape,
+                                                                            tuple(masks_dev.shape[1:])))
+                sel = masks_dev if len(kept) == len(params) else masks_dev[kept]
+                evaluator.add_image(sel, [self.label_to_id[params[k][2]] for k in kept], [float(c) for c in confs],
+                                    gt_ids)
+            if not write_files:
+                continue
+            masks = masks_dev.cpu().numpy()
             with open(os.path.join(save_dir, base.replace(".png", ".txt")), "w") as text_file:
-                for (pts, score, label, depth), mask, nz in zip(params, masks, counts):
-                    if label not in self.no_mask_labels and nz > 100:
-                        name = base.replace(".png", "_" + str(count) + ".png")
-                        text_file.write("masks/" + name + " " + str(self.label_to_id[label]) + " "
-                                        + str(min(1, score * 1.2)) + "\n")
-                        count += 1
-                        Image.fromarray(mask).save(os.path.join(masks_dir, name))
+                for count, (k, conf) in enumerate(zip(kept, confs)):
+                    name = base.replace(".png", "_" + str(count) + ".png")
+                    text_file.write("masks/" + name + " " + str(self.label_to_id[params[k][2]]) + " " + conf + "\n")
+                    Image.fromarray(masks[k]).save(os.path.join(masks_dir, name))
 
 
 class CITYSCAPES(CityscapesWriterMixin, PolygonDataset):
@@ -195,14 +220,30 @@ class CITYSCAPES(CityscapesWriterMixin, PolygonDataset):
         return "%s%d_regular_interval.json" % ("val" if split == "val" else "train", self.opt.nbr_points)
 
     def run_eval(self, results, save_dir):
-        """cityscapes.py:400-432 up to the vendored evaluator: results.json + the per-image mask files the
-        Cityscapes instance-level evaluation reads (evalInstanceLevelSemanticLabeling itself is outside the
-        accelerated path)."""
+        """cityscapes.py:400-432: results.json + the per-image mask files the Cityscapes instance-level evaluation
+        reads.  With --gt_dir the masks are also scored on the device (evaluation/instance_level.py), the evaluator's
+        table is printed, its JSON written and allAp returned; --no_mask_files then skips the mask and text files.
+        Without --gt_dir nothing is scored and the return value is 0.0."""
         super(CITYSCAPES, self).run_eval(results, save_dir)
         res_dir = os.path.join(save_dir, "results")
         os.makedirs(res_dir, exist_ok=True)
-        self.format_and_write_to_cityscapes(results, res_dir)
-        return 0.0
+        gt_dir = getattr(self.opt, "gt_dir", "")
+        if not gt_dir:
+            self.format_and_write_to_cityscapes(results, res_dir)
+            return 0.0
+        from ..evaluation import instance_level
+        if not os.path.isdir(gt_dir):
+            raise FileNotFoundError("--gt_dir %s is not a directory" % gt_dir)
+        evaluator = instance_level.InstanceLevelEvaluator()
+        self.format_and_write_to_cityscapes(results, res_dir, evaluator, instance_level.find_gt_files(gt_dir),
+                                            write_files=not getattr(self.opt, "no_mask_files", False))
+        res = evaluator.summarize()
+        print(instance_level.format_results(res))
+        out_dir = os.path.join(res_dir, "evaluationResults")
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "resultInstanceLevelSemanticLabeling.json"), "w") as f:
+            json.dump(instance_level.results_json(res), f, indent=4)
+        return res["allAp"]
 
 
 class KITTIPOLY(PolygonDataset):

@@ -1,0 +1,279 @@
+"""Cityscapes instance-level AP (the protocol of cityscapesscripts' evalInstanceLevelSemanticLabeling, the
+`distanceAvailable = False` case the reference runs after test.py), written from the algorithm.
+
+The pixel work -- one count per (predicted mask, ground-truth instance) pair, the void overlap, the mask sizes and
+the ground-truth table -- is done on the device by cp_instance_overlaps / cp_id_histogram from the masks
+cp_instance_masks leaves there and the 16-bit `*_gtFine_instanceIds.png` image.  This module keeps the small count
+tables per image and turns them into the AP numbers in float64 on the host.
+
+Per image and per class the protocol holds, for every threshold t in OVERLAPS:
+  * ground truths: ids >= 1000 of the class with at least MIN_REGION_SIZE pixels (ids below 1000 are groups);
+  * a prediction matches a ground truth when IoU = inter / (gt + pred - inter) > t.  The first match of a ground
+    truth is a true positive with the prediction's confidence; every further match makes a false positive that
+    carries the lower of the two confidences, the ground truth keeping the higher;
+  * a prediction that matches no ground truth of its class (groups and small ones included) is a false positive,
+    unless its share of void + group + small-instance pixels exceeds t: then it is dropped;
+  * a ground truth nobody matched is a hard false negative.
+Precision / recall are taken at the unique scores, AP is the precision weighted by the recall steps of the
+[-0.5, 0, 0.5] convolution; 0.0 for a class with ground truth and no prediction, nan for a class without ground truth."""
+import fnmatch
+import os
+import warnings
+
+import numpy as np
+
+INST_LABELS = ("person", "rider", "car", "truck", "bus", "train", "motorcycle", "bicycle")
+LABEL_IDS = (24, 25, 26, 27, 28, 31, 32, 33)
+# labels with ignoreInEval (-1, the licence plate, never matches a 16-bit pixel)
+VOID_IDS = (0, 1, 2, 3, 4, 5, 6, 9, 10, 14, 15, 16, 18, 29, 30, -1)
+OVERLAPS = np.arange(0.5, 1.0, 0.05)
+MIN_REGION_SIZES = np.array([100, 1000, 1000])          # only the first is used without distances
+MIN_REGION_SIZE = 100
+GT_SUFFIX = "_gtFine_instanceIds.png"
+MAX_MASKS, MAX_INST = 128, 1024                          # limits of cp_instance_overlaps
+
+
+def gt_instances(hist):
+    """The ground-truth table of one image from its id histogram (int [65536]): int64 [G, 3] rows
+    (instID, labelID, pixelCount) of the ids whose label is one of the eight, ascending instID."""
+    hist = np.asarray(hist)
+    ids = np.flatnonzero(hist)
+    labels = np.where(ids < 1000, ids, ids // 1000)
+    keep = np.isin(labels, LABEL_IDS)
+    return np.stack([ids[keep], labels[keep], hist[ids[keep]]], 1).astype(np.int64).reshape(-1, 3)
+
+
+def read_gt_ids(path):
+    """A `*_gtFine_instanceIds.png` as uint16 [H, W] (PIL hands it over as uint16 or as 32-bit mode I)."""
+    from PIL import Image
+    arr = np.array(Image.open(path))
+    if arr.ndim != 2 or arr.dtype.kind not in "iu":
+        raise ValueError("%s is not a single-channel integer id image (shape %s, %s)" % (path, arr.shape, arr.dtype))
+    if arr.size and (arr.min() < 0 or arr.max() > 65535):
+        raise ValueError("%s holds ids outside 16 bits (%d .. %d)" % (path, arr.min(), arr.max()))
+    return np.ascontiguousarray(arr.astype(np.uint16))
+
+
+def find_gt_files(gt_dir):
+    """{image prefix: path} of every *_gtFine_instanceIds.png below gt_dir."""
+    out = {}
+    for root, _, files in os.walk(gt_dir):
+        for f in fnmatch.filter(files, "*" + GT_SUFFIX):
+            key = f[:-len(GT_SUFFIX)]
+            if key in out:
+                raise ValueError("two ground-truth files for %s: %s and %s" % (key, out[key], os.path.join(root, f)))
+            out[key] = os.path.join(root, f)
+    return out
+
+
+def device_counts(masks_dev, gt_dev, inst_ids):
+    """cp_instance_overlaps on device masks uint8 [n, H, W] and device ids [H, W] (16-bit elements):
+    (inter [n, G], void_inter [n], pred_pixels [n]) as host int64 arrays."""
+    import torch
+
+    from ... import _C
+    n, H, W = masks_dev.shape
+    G = len(inst_ids)
+    dev = masks_dev.device
+    inst = torch.tensor(list(inst_ids), dtype=torch.int32).to(dev)
+    void = torch.tensor(VOID_IDS, dtype=torch.int32).to(dev)
+    out = torch.empty((n * G + 2 * n,), dtype=torch.int32, device=dev)
+    L = _C.lib()
+    nbytes = L.cp_instance_overlaps_workspace_bytes(n, G, H, W)
+    ws = _C.workspace(nbytes, dev)
+    _C.check(L.cp_instance_overlaps(_C.ptr(masks_dev), n, _C.ptr(gt_dev), H, W, _C.ptr(inst), G, _C.ptr(void),
+                                    len(VOID_IDS), _C.ptr(out[:n * G]), _C.ptr(out[n * G:n * G + n]),
+                                    _C.ptr(out[n * G + n:]), _C.ptr(ws), nbytes, _C.stream()), "cp_instance_overlaps")
+    host = out.cpu().numpy().astype(np.int64)
+    return host[:n * G].reshape(n, G), host[n * G:n * G + n], host[n * G + n:]
+
+
+def device_histogram(gt_dev):
+    """cp_id_histogram of device ids [H, W] (16-bit elements): host int64 [65536]."""
+    import torch
+
+    from ... import _C
+    H, W = gt_dev.shape
+    hist = torch.empty((65536,), dtype=torch.int32, device=gt_dev.device)
+    _C.check(_C.lib().cp_id_histogram(_C.ptr(gt_dev), H, W, _C.ptr(hist), _C.stream()), "cp_id_histogram")
+    return hist.cpu().numpy().astype(np.int64)
+
+
+class InstanceLevelEvaluator(object):
+    """Collects the count tables image by image (add_image / add_counts) and scores them (summarize)."""
+
+    def __init__(self):
+        self.images = []
+
+    def add_counts(self, gt_table, label_ids, confidences, pred_pixels, void_inter, inter):
+        """One image from its counts: gt_table [G, 3] as gt_instances returns it; per prediction its label id,
+        confidence, pixel count and void overlap; inter [n, G], column j counted against gt_table[j].  Predictions
+        with a label outside the eight or without pixels are skipped, as the protocol skips them."""
+        gt_table = np.asarray(gt_table, np.int64).reshape(-1, 3)
+        inter = np.asarray(inter, np.int64).reshape(len(label_ids), len(gt_table))
+        preds = []
+        for i, (lab, conf) in enumerate(zip(label_ids, confidences)):
+            if int(lab) not in LABEL_IDS or int(pred_pixels[i]) == 0:
+                continue
+            preds.append((int(lab), float(conf), int(pred_pixels[i]), int(void_inter[i]), inter[i]))
+        self.images.append((gt_table, preds))
+
+    def add_image(self, masks_dev, label_ids, confidences, gt_ids):
+        """One image from device masks uint8 [n, H, W] (any n: the kernel is called on slices of 128) and its id
+        image: a host uint16 [H, W] array, or a device tensor of 16-bit elements holding those bits."""
+        import torch
+        n = int(masks_dev.shape[0])
+        if not torch.is_tensor(gt_ids):
+            gt_ids = np.ascontiguousarray(gt_ids)
+            if gt_ids.dtype != np.uint16:
+                raise ValueError("gt_ids must be uint16 (see read_gt_ids), got %s" % gt_ids.dtype)
+            dev = masks_dev.device if n else torch.device("cuda")         # (an image without predictions still
+            gt_ids = torch.from_numpy(gt_ids.view(np.int16)).to(dev)      # has ground truth to count; bits are kept)
+        if len(label_ids) != n or len(confidences) != n:
+            raise ValueError("%d masks, %d labels, %d confidences" % (n, len(label_ids), len(confidences)))
+        if tuple(masks_dev.shape[1:]) != tuple(gt_ids.shape):
+            raise ValueError("masks are %s, the id image is %s" % (tuple(masks_dev.shape[1:]), tuple(gt_ids.shape)))
+        table = gt_instances(device_histogram(gt_ids))
+        G = len(table)
+        inter = np.zeros((n, G), np.int64)
+        void = np.zeros((n,), np.int64)
+        pix = np.zeros((n,), np.int64)
+        for a in range(0, n, MAX_MASKS):
+            for g in range(0, max(G, 1), MAX_INST):
+                i, v, p = device_counts(masks_dev[a:a + MAX_MASKS], gt_ids, table[g:g + MAX_INST, 0])
+                inter[a:a + MAX_MASKS, g:g + MAX_INST], void[a:a + MAX_MASKS], pix[a:a + MAX_MASKS] = i, v, p
+        self.add_counts(table, label_ids, confidences, pix, void, inter)
+
+    def ap_matrix(self):
+        """float64 [1, 8, 10]: AP per (region size setting, class, overlap threshold)."""
+        ap = np.zeros((1, len(LABEL_IDS), len(OVERLAPS)), np.float64)
+        for oi, th in enumerate(OVERLAPS):
+            for li, lab in enumerate(LABEL_IDS):
+                ap[0, li, oi] = self._class_ap(lab, th)
+        return ap
+
+    def _class_ap(self, lab, th):
+        y_true, y_score = [], []
+        hard_fn = 0
+        have_gt = have_pred = False
+        for table, preds in self.images:
+            cols = np.flatnonzero(table[:, 1] == lab)                      # every id of the class, groups included
+            ids, size = table[cols, 0], table[cols, 2]
+            real = (ids >= 1000) & (size >= MIN_REGION_SIZE)
+            ignore = (ids < 1000).astype(np.int64) + (size < MIN_REGION_SIZE)   # a small group counts twice
+            mine = [p for p in preds if p[0] == lab]
+            have_gt |= bool(real.any())
+            have_pred |= bool(mine)
+            best = {}                                                       # ground truth -> score it holds
+            for _, conf, pix, void, row in mine:
+                inter = row[cols]
+                hit = inter > 0
+                iou = np.where(hit, inter / np.maximum(size + pix - inter, 1).astype(np.float64), 0.0)
+                over = hit & (iou > th)
+                for g in np.flatnonzero(over & real):
+                    if g in best:
+                        y_true.append(0.0)
+                        y_score.append(min(best[g], conf))
+                        best[g] = max(best[g], conf)
+                    else:
+                        best[g] = conf
+                if not over.any():
+                    if float(void + int((inter * ignore).sum())) / pix <= th:
+                        y_true.append(0.0)
+                        y_score.append(conf)
+            hard_fn += int(real.sum()) - len(best)
+            y_true.extend([1.0] * len(best))
+            y_score.extend(best.values())
+        if not have_gt:
+            return float("nan")
+        if not have_pred:
+            return 0.0
+        y_true, y_score = np.array(y_true, np.float64), np.array(y_score, np.float64)
+        order = np.argsort(y_score, kind="stable")
+        score, true = y_score[order], y_true[order]
+        cum = np.append(np.cumsum(true), 0.0)                             # index -1: nothing below the first score
+        _, first = np.unique(score, return_index=True)
+        n_true = cum[-2] if len(true) else 0.0
+        precision = np.zeros(len(first) + 1)
+        recall = np.zeros(len(first) + 1)
+        for k, idx in enumerate(first):
+            below = cum[idx - 1]
+            tp = n_true - below
+            fp = len(score) - idx - tp
+            fn = below + hard_fn
+            precision[k] = tp / (tp + fp)
+            recall[k] = tp / (tp + fn)
+        precision[-1], recall[-1] = 1.0, 0.0
+        steps = np.convolve(np.concatenate([recall[:1], recall, [0.0]]), [-0.5, 0, 0.5], "valid")
+        return float(np.dot(precision, steps))
+
+    def summarize(self):
+        """The evaluator's dictionary (allAp, allAp50%, classes[name][ap | ap50%]) plus "resultApMatrix"."""
+        ap = self.ap_matrix()
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", RuntimeWarning)             # no ground truth at all: nan, not a warning
+            res = {"allAp": float(np.nanmean(ap[0])), "allAp50%": float(np.nanmean(ap[0, :, 0])), "classes": {}}
+        for li, name in enumerate(INST_LABELS):
+            res["classes"][name] = {"ap": float(np.average(ap[0, li])), "ap50%": float(ap[0, li, 0])}
+        res["resultApMatrix"] = ap
+        return res
+
+
+def results_json(res):
+    """The dictionary the evaluator writes as resultInstanceLevelSemanticLabeling.json."""
+    return {"averages": {k: v for k, v in res.items() if k != "resultApMatrix"}, "overlaps": OVERLAPS.tolist(),
+            "minRegionSizes": MIN_REGION_SIZES.tolist(), "instLabels": list(INST_LABELS),
+            "resultApMatrix": res["resultApMatrix"].tolist()}
+
+
+def format_results(res):
+    """The evaluator's result table as text."""
+    lines = ["", "#" * 50, "{:<15}".format("what") + ":" + "{:>15}".format("AP") + "{:>15}".format("AP_50%"), "#" * 50]
+    for name in INST_LABELS:
+        c = res["classes"][name]
+        lines.append("{:<15}".format(name) + ":" + "{:>15.3f}".format(c["ap"]) + "{:>15.3f}".format(c["ap50%"]))
+    lines += ["-" * 50, "{:<15}".format("average") + ":" + "{:>15.3f}".format(res["allAp"])
+              + "{:>15.3f}".format(res["allAp50%"]), ""]
+    return "\n".join(lines)
+
+
+def read_pred_info(txt_path):
+    """The lines `relative mask path, label id, confidence` of one result file."""
+    out = []
+    with open(txt_path) as f:
+        for line in f:
+            parts = line.split(" ")
+            if len(parts) != 3:
+                raise ValueError("%s: expected `maskPath labelID confidence`, got %r" % (txt_path, line))
+            if os.path.isabs(parts[0]):
+                raise ValueError("%s: mask paths must be relative (%s)" % (txt_path, parts[0]))
+            out.append((os.path.join(os.path.dirname(txt_path), parts[0]), int(float(parts[1])), float(parts[2])))
+    return out
+
+
+def evaluate_result_dir(pred_dir, gt_files, device=None):
+    """Scores a result directory in the Cityscapes layout (`<image>*.txt` listing `masks/*.png`, searched below
+    pred_dir by the prefix of each ground-truth file).  Masks are uploaded image by image."""
+    import torch
+    from PIL import Image
+    dev = device or torch.device("cuda")
+    txts = [os.path.join(r, f) for r, _, files in os.walk(pred_dir) for f in files if f.endswith(".txt")]
+    ev = InstanceLevelEvaluator()
+    for gt in gt_files:
+        base = os.path.basename(gt)
+        prefix = base[:-len(GT_SUFFIX)] if base.endswith(GT_SUFFIX) else os.path.splitext(base)[0]
+        mine = [t for t in txts if fnmatch.fnmatch(os.path.basename(t), prefix + "*.txt")]
+        if len(mine) != 1:
+            raise FileNotFoundError("%d prediction files %s*.txt below %s for ground truth %s"
+                                    % (len(mine), prefix, pred_dir, gt))
+        ids = read_gt_ids(gt)
+        info = read_pred_info(mine[0])
+        info = [p for p in info if p[1] in LABEL_IDS]                      # other labels are never opened
+        masks = np.zeros((len(info),) + ids.shape, np.uint8)
+        for k, (path, _, _) in enumerate(info):
+            m = np.array(Image.open(path).convert("L"))
+            if m.shape != ids.shape:
+                raise ValueError("%s is %s, the ground truth %s is %s" % (path, m.shape, gt, ids.shape))
+            masks[k] = m
+        ev.add_image(torch.from_numpy(masks).to(dev), [p[1] for p in info], [p[2] for p in info], ids)
+    return ev.summarize()

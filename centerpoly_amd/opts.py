@@ -96,6 +96,11 @@ class opts(object):
         p.add_argument("--K", type=int, default=128)
         p.add_argument("--thresh", type=float, default=0.05,
                        help="threshold for the outputs kept for evaluation (result writer)")
+        p.add_argument("--gt_dir", default="",
+                       help="directory searched recursively for <city>_<seq>_<frame>_gtFine_instanceIds.png: with it "
+                            "run_eval scores the masks on the GPU (Cityscapes instance-level AP); empty: files only")
+        p.add_argument("--no_mask_files", action="store_true",
+                       help="with --gt_dir: score in memory and skip the PNG and text output")
         p.add_argument("--not_prefetch_test", action="store_true")
         p.add_argument("--fix_res", action="store_true")
         p.add_argument("--keep_res", action="store_true")
@@ -128,6 +133,9 @@ class opts(object):
             # opts.py never defines: the combination has no target semantics to follow
             self.parser.error("--elliptical_gt cannot be combined with --mse_loss: the reference sizes --mse_loss "
                               "targets by --hm_gauss, which it never defines")
+        if opt.no_mask_files and not opt.gt_dir:
+            self.parser.error("--no_mask_files needs --gt_dir: without a ground truth to score against, the mask files "
+                              "are the only result of the evaluation")
         opt.gpus_str = opt.gpus
         from . import arithmetic
         arithmetic.configure(opt.arithmetic)

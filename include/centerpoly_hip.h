@@ -392,6 +392,32 @@ int cp_conv1x1_act_forward(const float* y, int64_t y_bstride, const float* in_bi
 int cp_instance_masks(const int32_t* poly, const uint8_t* flags, int32_t n, int32_t N, int32_t H, int32_t W,
                       uint8_t* masks, int32_t* counts, void* stream);
 
+/* ------------------------------------------------ instance-level evaluation --
+ * The pixel counting of the Cityscapes instance-level AP (evalInstanceLevelSemanticLabeling.assignGt2Preds and
+ * instances2dict of the cityscapesscripts): every count the protocol needs of one image, from the masks
+ * cp_instance_masks left on the device and the 16-bit `*_gtFine_instanceIds.png` image.  Integer counts, exact.
+ *
+ * cp_id_histogram: hist[v] = number of pixels of value v (np.unique + one (img == id).sum() per id, one pass).
+ *   ids   DEVICE uint16 [H][W]                 hist  DEVICE int32 [65536] out (zeroed here)
+ *
+ * cp_instance_overlaps:
+ *   masks     DEVICE uint8 [n][H][W], non-zero = inside      gt_ids   DEVICE uint16 [H][W]
+ *   inst_ids  DEVICE int32 [G], distinct values of interest  void_ids DEVICE int32 [V] (values outside 16 bits
+ *                                                                      match no pixel)
+ *   inter       DEVICE int32 [n][G] out: pixels where mask i is set and gt_ids == inst_ids[j]
+ *   void_inter  DEVICE int32 [n]    out: pixels where mask i is set and the RAW pixel value is one of void_ids
+ *   pred_pixels DEVICE int32 [n]    out: non-zero pixels of mask i
+ * n <= 128, G <= 1024, V <= 64, H * W < 2^31 (CP_EUNSUPPORTED otherwise); any H, W and any alignment (16-byte
+ * aligned masks with H * W % 16 == 0 take the wide loads).  A fixed number of launches whatever n and G.
+ * workspace: cp_instance_overlaps_workspace_bytes (the id -> column table); shorter: CP_EWORKSPACE.  All checks
+ * come before any device work. */
+int cp_id_histogram(const uint16_t* ids, int32_t H, int32_t W, int32_t* hist, void* stream);
+size_t cp_instance_overlaps_workspace_bytes(int32_t n, int32_t G, int32_t H, int32_t W);
+int cp_instance_overlaps(const uint8_t* masks, int32_t n, const uint16_t* gt_ids, int32_t H, int32_t W,
+                         const int32_t* inst_ids, int32_t G, const int32_t* void_ids, int32_t V, int32_t* inter,
+                         int32_t* void_inter, int32_t* pred_pixels, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* ------------------------------------------------ detector pre/post-processing --
  * cp_preprocess_warp_normalize: the cv2 stage of BaseDetector.pre_process
  * (src/lib/detectors/base_detector.py:66-87): cv2.warpAffine(image, trans_input, (dst_w, dst_h),
