@@ -52,6 +52,7 @@ class PolygonDataset(data.Dataset):
     _valid_ids = [1, 2, 3, 4, 5, 6, 7, 8]
     annot_subdir = ""
     name = ""
+    scores_ap = False                                        # run_eval writes results.json and scores nothing
 
     def annot_file(self, split):
         raise NotImplementedError
@@ -159,6 +160,96 @@ class CityscapesWriterMixin(object):
         masks, counts = self.instance_masks_device(params, device)
         return masks.cpu().numpy(), counts.cpu().numpy()
 
+    def class_table(self):
+        """cp_writer_instances' table: int32 [C, 2] rows (label id, label has masks) of class 0 .. C-1."""
+        names = self.class_name[1:]
+        return np.array([[self.label_to_id[c], 0 if c in self.no_mask_labels else 1] for c in names], np.int32)
+
+    def score_instances_device(self, rows_dev, gt_ids, gt_table=None, evaluator=None):
+        """One image scored from its detection rows without a pass through host Python: device float32 rows
+        [R, 2N + 7] in the layout cp_polydet_post_process writes (x1,y1,x2,y2,score,cls,poly,depth; R <= 1024)
+        -> cp_writer_instances -> cp_instance_masks -> cp_instance_overlaps on all slots, then ONE read of the small
+        tables.  gt_ids: host uint16 [H, W] (see read_gt_ids) or a device tensor of 16-bit elements; gt_table: what
+        instance_level.gt_instances gives for it (a loader worker can make it from np.bincount), by default taken
+        from cp_id_histogram.  The writer's selection (label has masks, more than 100 pixels) is applied to the rows
+        of the tables; with an `evaluator` the kept rows are added to it (add_counts).  Returns the tables:
+        n, src, labels, conf (float32), conf_text, counts, kept, gt_table, inter, void."""
+        import ctypes
+
+        import torch
+
+        from ... import _C
+        from ..evaluation import instance_level as il
+        W, H = self.canvas
+        if rows_dev.dim() != 2 or rows_dev.dtype != torch.float32 or rows_dev.shape[1] < 13 or rows_dev.shape[1] % 2 == 0:
+            raise ValueError("rows must be float32 [R, 2N + 7], got %s %s" % (rows_dev.dtype, tuple(rows_dev.shape)))
+        dev = rows_dev.device
+        R, N = int(rows_dev.shape[0]), (int(rows_dev.shape[1]) - 7) // 2
+        if R == 0:                                                         # no detection at all: one dead row
+            rows_dev = torch.full((1, 2 * N + 7), float("-inf"), dtype=torch.float32, device=dev)
+            R = 1
+        S = min(R, il.MAX_MASKS)                                          # slots drawn and counted
+        if torch.is_tensor(gt_ids):
+            gt_dev = gt_ids
+        else:
+            gt_ids = np.ascontiguousarray(gt_ids)
+            if gt_ids.dtype != np.uint16:
+                raise ValueError("gt_ids must be uint16 (see read_gt_ids), got %s" % gt_ids.dtype)
+            gt_dev = torch.from_numpy(gt_ids.view(np.int16)).to(dev)
+        if tuple(gt_dev.shape) != (H, W):
+            raise ValueError("the id image is %s, the result canvas is %s" % (tuple(gt_dev.shape), (H, W)))
+        if gt_table is None:
+            gt_table = il.gt_instances(il.device_histogram(gt_dev))
+        gt_table = np.asarray(gt_table, np.int64).reshape(-1, 3)
+        G = len(gt_table)
+        G0 = min(G, il.MAX_INST)
+        L = _C.lib()
+        table = np.ascontiguousarray(self.class_table())
+        # one upload: the ids of interest and the void ids; one buffer for everything that comes back
+        ids = torch.from_numpy(np.concatenate([gt_table[:G0, 0], il.VOID_IDS]).astype(np.int32)).to(dev)
+        fw = (R + 3) // 4
+        out = torch.empty((4 + 3 * R + 3 * S + fw + S * G0,), dtype=torch.int32, device=dev)
+        o_src, o_lab, o_conf = 4, 4 + R, 4 + 2 * R
+        o_cnt = 4 + 3 * R
+        o_void, o_pix, o_flag, o_int = o_cnt + S, o_cnt + 2 * S, o_cnt + 3 * S, o_cnt + 3 * S + fw
+        poly = torch.empty((R, N, 2), dtype=torch.int32, device=dev)
+        masks = torch.empty((S, H, W), dtype=torch.uint8, device=dev)
+        at = lambda o: ctypes.c_void_p(out.data_ptr() + 4 * o)            # noqa: E731
+        st = _C.stream()
+        _C.check(L.cp_writer_instances(_C.ptr(rows_dev), R, N, float(self.opt.thresh),
+                                       table.ctypes.data_as(ctypes.c_void_p), len(table), at(0), at(o_src),
+                                       _C.ptr(poly), at(o_flag), at(o_lab), at(o_conf), st), "cp_writer_instances")
+        _C.check(L.cp_instance_masks(_C.ptr(poly), at(o_flag), S, N, H, W, _C.ptr(masks), at(o_cnt), st),
+                 "cp_instance_masks")
+        nbytes = L.cp_instance_overlaps_workspace_bytes(S, G0, H, W)
+        ws = _C.workspace(nbytes, dev)
+        _C.check(L.cp_instance_overlaps(_C.ptr(masks), S, _C.ptr(gt_dev), H, W, _C.ptr(ids), G0,
+                                        ctypes.c_void_p(ids.data_ptr() + 4 * G0), len(il.VOID_IDS), at(o_int),
+                                        at(o_void), at(o_pix), _C.ptr(ws), nbytes, st), "cp_instance_overlaps")
+        host = out.cpu().numpy()
+        n = int(host[0])
+        if n > il.MAX_MASKS:
+            raise ValueError("more than 128 instances in one image (max_per_image = K <= 128)")
+        flags = host[o_flag:o_flag + fw].view(np.uint8)[:n]
+        counts = host[o_cnt:o_cnt + n].astype(np.int64)
+        inter = host[o_int:o_int + S * G0].reshape(S, G0)[:n].astype(np.int64)
+        for g in range(il.MAX_INST, G, il.MAX_INST):                      # more ids than one call takes: rare
+            more = il.device_counts(masks, gt_dev, gt_table[g:g + il.MAX_INST, 0])[0]
+            inter = np.concatenate([inter, more[:n]], axis=1)
+        conf = host[o_conf:o_conf + n].view(np.float32)
+        res = {"n": n, "src": host[o_src:o_src + n].copy(), "labels": host[o_lab:o_lab + n].astype(np.int64),
+               "conf": conf.copy(), "counts": counts, "gt_table": gt_table, "inter": inter,
+               "void": host[o_void:o_void + n].astype(np.int64)}
+        # the writer's selection and the confidence as the text line spells it (what the evaluator reads back)
+        kept = [k for k in range(n) if flags[k] & 1 and counts[k] > 100]
+        res["kept"] = kept
+        res["conf_text"] = [str(min(1, conf[k])) for k in kept]
+        if evaluator is not None:
+            pix = host[o_pix:o_pix + n].astype(np.int64)
+            evaluator.add_counts(gt_table, res["labels"][kept].tolist(), [float(c) for c in res["conf_text"]],
+                                 pix[kept], res["void"][kept], inter[kept])
+        return res
+
     def format_and_write_to_cityscapes(self, all_bboxes, save_dir, evaluator=None, gt_files=None, write_files=True):
         """Writes the result files; with an `evaluator` (evaluation.instance_level.InstanceLevelEvaluator) the kept
         masks are also scored against `gt_files` ({image prefix: id image path}) while they are on the device."""
@@ -213,6 +304,7 @@ class CITYSCAPES(CityscapesWriterMixin, PolygonDataset):
 
     label_to_id = {"person": 24, "rider": 25, "car": 26, "truck": 27, "bus": 28, "train": 31, "motorcycle": 32,
                    "bicycle": 33, "pole": -1, "traffic sign": -1, "traffic light": -1}
+    scores_ap = True                                         # run_eval returns the instance-level AP with --gt_dir
 
     def annot_file(self, split):
         if split == "test":
@@ -237,6 +329,12 @@ class CITYSCAPES(CityscapesWriterMixin, PolygonDataset):
         evaluator = instance_level.InstanceLevelEvaluator()
         self.format_and_write_to_cityscapes(results, res_dir, evaluator, instance_level.find_gt_files(gt_dir),
                                             write_files=not getattr(self.opt, "no_mask_files", False))
+        return self.report_eval(evaluator, res_dir)
+
+    def report_eval(self, evaluator, res_dir):
+        """The evaluator's table on the screen, its JSON below res_dir; returns allAp."""
+        from ..evaluation import instance_level
+        self.last_evaluator = evaluator
         res = evaluator.summarize()
         print(instance_level.format_results(res))
         out_dir = os.path.join(res_dir, "evaluationResults")
@@ -244,6 +342,16 @@ class CITYSCAPES(CityscapesWriterMixin, PolygonDataset):
         with open(os.path.join(out_dir, "resultInstanceLevelSemanticLabeling.json"), "w") as f:
             json.dump(instance_level.results_json(res), f, indent=4)
         return res["allAp"]
+
+    def finish_scored_eval(self, results, save_dir, evaluator):
+        """run_eval for a run whose images were already scored as they passed (score_instances_device with
+        `evaluator`): results.json, the mask and text files through the writer unless --no_mask_files, the report."""
+        PolygonDataset.run_eval(self, results, save_dir)
+        res_dir = os.path.join(save_dir, "results")
+        os.makedirs(res_dir, exist_ok=True)
+        if not getattr(self.opt, "no_mask_files", False):
+            self.format_and_write_to_cityscapes(results, res_dir)
+        return self.report_eval(evaluator, res_dir)
 
 
 class KITTIPOLY(PolygonDataset):

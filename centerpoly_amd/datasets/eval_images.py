@@ -1,0 +1,63 @@
+"""The image list of test.py (reference: src/test.py:23-44 PrefetchDataset and :99-112): `dataset.images` ->
+`coco.loadImgs` -> `read_image`, one item per image.  An item is decoded on the host only, so the items can come from
+`DataLoader` workers while the detector runs: the 8-bit BGR image and, when ground truth is scored, the 16-bit id
+image with its ground-truth table (`gt_instances` on an `np.bincount`, so no histogram has to come back from the
+device before the overlap kernel starts).  A missing image or ground-truth file is an error that names the path."""
+import os
+
+import numpy as np
+import torch.utils.data as data
+
+from .evaluation import instance_level
+
+
+def image_prefix(file_name):
+    """`frankfurt_000000_000294` of `.../frankfurt_000000_000294_leftImg8bit.png`: the key of the ground truth."""
+    base = os.path.basename(file_name)
+    return base[:-len("_leftImg8bit.png")] if base.endswith("_leftImg8bit.png") else os.path.splitext(base)[0]
+
+
+class EvalImages(data.Dataset):
+    def __init__(self, dataset, gt_files=None):
+        self.dataset = dataset
+        self.gt_files = gt_files                               # {image prefix: id image path} or None
+
+    def __len__(self):
+        return len(self.dataset.images)
+
+    def info(self, ind):
+        """(image id, file name as the annotation file gives it)."""
+        img_id = self.dataset.images[ind]
+        return img_id, self.dataset.coco.loadImgs(ids=[img_id])[0]["file_name"]
+
+    def gt_path(self, file_name):
+        prefix = image_prefix(file_name)
+        if prefix not in self.gt_files:
+            raise FileNotFoundError("no ground truth %s%s below --gt_dir for image %s"
+                                    % (prefix, instance_level.GT_SUFFIX, os.path.basename(file_name)))
+        return self.gt_files[prefix]
+
+    def __getitem__(self, ind):
+        img_id, file_name = self.info(ind)
+        item = {"img_id": img_id, "image": self.dataset.read_image(file_name)}
+        if self.gt_files is not None:
+            path = self.gt_path(file_name)
+            if not os.path.isfile(path):
+                raise FileNotFoundError("ground truth %s not found" % path)
+            ids = instance_level.read_gt_ids(path)
+            item["gt_ids"] = ids
+            item["gt_table"] = instance_level.gt_instances(np.bincount(ids.reshape(-1), minlength=65536))
+        return item
+
+
+def _first(batch):
+    return batch[0]
+
+
+def iterate(images, prefetch, num_workers):
+    """The items in order: a plain loop, or a DataLoader whose `num_workers` workers decode ahead of the consumer
+    (batches of one, handed over as they are: the arrays are not collated into tensors)."""
+    if not prefetch:
+        return (images[i] for i in range(len(images)))
+    return data.DataLoader(images, batch_size=1, shuffle=False, num_workers=max(0, int(num_workers)),
+                           collate_fn=_first, pin_memory=False)

@@ -38,8 +38,20 @@ class PolydetDetector(BaseDetector):
     def post_process(self, dets, meta, scale=1, fg=None):
         # transform_preds + `/ scale` on the device, one copy back, class split on the host
         dets = dets.detach().reshape(1, -1, dets.shape[2])
-        return polydet_post_process_device(dets, [meta["c"]], [meta["s"]], meta["out_height"],
-                                           meta["out_width"], self.opt.num_classes, scale)[0]
+        ret, rows = polydet_post_process_device(dets, [meta["c"]], [meta["s"]], meta["out_height"],
+                                                meta["out_width"], self.opt.num_classes, scale, return_device=True)
+        self.rows_dev = rows[0]                      # the same rows, still on the device (see device_rows)
+        return ret[0]
+
+    def device_rows(self, results=None):
+        """The detections of the last run() as device rows [R, 2N+7] (x1,y1,x2,y2,score,cls,poly,depth), what
+        CityscapesWriterMixin.score_instances_device reads.  One scale without --nms: the rows post_process left
+        on the device, no copy.  Otherwise merge_outputs ran on the host: its `results` are uploaded."""
+        if len(self.scales) == 1 and not self.opt.nms:
+            return self.rows_dev
+        rows = [np.concatenate([r[:, :5], np.full((len(r), 1), j - 1, np.float32), r[:, 5:]], axis=1)
+                for j, r in sorted(results.items())]
+        return torch.from_numpy(np.ascontiguousarray(np.concatenate(rows, axis=0), np.float32)).to(self.opt.device)
 
     def merge_outputs(self, detections):
         results = {}

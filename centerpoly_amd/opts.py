@@ -43,7 +43,9 @@ class opts(object):
         p.add_argument("--print_iter", type=int, default=0)
         p.add_argument("--hide_data_time", action="store_true")
         p.add_argument("--save_all", action="store_true")
-        p.add_argument("--metric", default="loss")
+        p.add_argument("--metric", default="loss",
+                       help="what picks model_best.pth: a validation loss statistic (loss, hm_l, poly_l, ...; lower "
+                            "is better) or `ap`, run_eval's instance-level AP (higher is better; needs --gt_dir)")
         # model
         p.add_argument("--arch", default="dla_34",
                        help="dla_34 | hourglass | smallhourglass")
@@ -136,6 +138,15 @@ class opts(object):
         if opt.no_mask_files and not opt.gt_dir:
             self.parser.error("--no_mask_files needs --gt_dir: without a ground truth to score against, the mask files "
                               "are the only result of the evaluation")
+        if opt.metric == "ap":
+            from .datasets.dataset_factory import dataset_factory
+            if not getattr(dataset_factory.get(opt.dataset), "scores_ap", False):
+                self.parser.error("--metric ap: run_eval of dataset %r writes result files and scores nothing, so "
+                                  "there is no AP to pick model_best.pth by (cityscapes scores; the others keep a "
+                                  "loss statistic)" % opt.dataset)
+            if not opt.gt_dir:
+                self.parser.error("--metric ap needs --gt_dir: without the *_gtFine_instanceIds.png ground truth "
+                                  "run_eval has nothing to score the validation masks against")
         opt.gpus_str = opt.gpus
         from . import arithmetic
         arithmetic.configure(opt.arithmetic)

@@ -418,6 +418,25 @@ int cp_instance_overlaps(const uint8_t* masks, int32_t n, const uint16_t* gt_ids
                          int32_t* void_inter, int32_t* pred_pixels, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* cp_writer_instances: the writer's selection for ONE image on the device -- image_instances plus the label, flag and
+ * confidence bookkeeping of format_and_write_to_cityscapes (cityscapes.py:225-238, 266-281) -- from detection rows in
+ * the layout cp_polydet_post_process writes to the instance list cp_instance_masks and the evaluator read.
+ *   rows   DEVICE fp32 [R][2N + 7]: x1,y1,x2,y2,score,cls,poly(2N),depth (cls counts from 0)
+ *   class_table  HOST int32 [C][2]: label id, "the label has masks" (non-zero) of class 0 .. C-1
+ *   n_out  DEVICE int32 [1]: live instances        src    DEVICE int32 [R]: source row of every instance
+ *   poly   DEVICE int32 [R][N][2]                  flags  DEVICE uint8 [R], the bits of cp_instance_masks
+ *   label  DEVICE int32 [R]                        conf   DEVICE fp32 [R]: min(1, score * 1.2f) in fp32
+ * A row is live when score > thresh (strict, fp32) and cls is an integer in [0, C).  Instances are in ascending
+ * depth, ties by class and then by row (the stable sort of the host loop; a NaN depth sorts last).  A vertex is
+ * int(float("%.2f" % v)) = sign(v) (floor|v| + (|v| - floor|v| > 0.995)) in fp64, saturated to int32.  Slots at n_out
+ * and above are dead: flags 0 (cp_instance_masks draws nothing), src and label -1, conf 0, vertices 0.  More than
+ * 128 live rows are reported through n_out; it is the caller's to refuse them before it reads the masks.
+ * 1 <= R <= 1024, 3 <= N <= 64, 1 <= C <= 32: beyond the upper limits CP_EUNSUPPORTED, otherwise (and for null
+ * pointers or a NaN threshold) CP_EINVAL, all before any device work.  One launch of one workgroup. */
+int cp_writer_instances(const float* rows, int32_t R, int32_t N, float thresh, const int32_t* class_table, int32_t C,
+                        int32_t* n_out, int32_t* src, int32_t* poly, uint8_t* flags, int32_t* label, float* conf,
+                        void* stream);
+
 /* ------------------------------------------------ detector pre/post-processing --
  * cp_preprocess_warp_normalize: the cv2 stage of BaseDetector.pre_process
  * (src/lib/detectors/base_detector.py:66-87): cv2.warpAffine(image, trans_input, (dst_w, dst_h),

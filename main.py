@@ -18,6 +18,7 @@ from centerpoly_amd.datasets.dataset_factory import get_dataset
 from centerpoly_amd.models.model import create_model, load_model, save_model
 from centerpoly_amd.opts import opts
 from centerpoly_amd.trains.train_factory import train_factory
+from centerpoly_amd.utils.utils import BestMetric
 
 
 def main(opt):
@@ -76,7 +77,7 @@ def main(opt):
     if rank == 0:
         os.makedirs(opt.save_dir, exist_ok=True)
     print("Starting training...")
-    best = 1e10
+    best = BestMetric(opt.metric)
     for epoch in range(start_epoch + 1, opt.num_epochs + 1):
         mark = epoch if opt.save_all else "last"
         if sampler is not None:
@@ -88,9 +89,8 @@ def main(opt):
                 save_model(os.path.join(opt.save_dir, "model_{}.pth".format(mark)), epoch, model, optimizer)
                 with torch.no_grad():
                     log_dict_val, preds = trainer.val(epoch, val_loader)
-                val_loader.dataset.run_eval(preds, opt.save_dir)
-                if log_dict_val[opt.metric] < best:
-                    best = log_dict_val[opt.metric]
+                ap = val_loader.dataset.run_eval(preds, opt.save_dir)
+                if best.update(ap if opt.metric == "ap" else log_dict_val[opt.metric]):
                     save_model(os.path.join(opt.save_dir, "model_best.pth"), epoch, model)
             else:
                 save_model(os.path.join(opt.save_dir, "model_last.pth"), epoch, model, optimizer)

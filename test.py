@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Evaluation driver with the reference's CLI and control flow (src/test.py:47-131):
-`python test.py polydet --arch dla_34 --load_model model_last.pth`.  Images come from the
-synthetic dataset (uint8 arrays through PolydetDetector.run, pre-process included)."""
+`python test.py polydet --arch dla_34 --load_model model_last.pth`.  `cityscapes`, `kitti_poly` and `IDD` read their
+image files (`dataset.images` -> `coco.loadImgs` -> `read_image`), by default through a prefetching DataLoader whose
+workers decode ahead of the detector, with --not_prefetch_test in a plain loop.  With --gt_dir on Cityscapes every
+image is scored on the device as it passes (CityscapesWriterMixin.score_instances_device) and the instance-level allAp
+is returned.  `--dataset synthetic` feeds hash-generated uint8 arrays (no files)."""
 import os
 import sys
 import time
@@ -18,7 +21,11 @@ from centerpoly_amd.opts import opts
 from centerpoly_amd.utils.utils import AverageMeter
 
 
-def test(opt):
+def run_test(opt, evaluate=True):
+    """One pass over the validation images: {"ap": run_eval's return value (None for the synthetic set),
+    "results": {image id: {class: rows}}, "dataset": the data set object (its last_evaluator holds the count
+    tables of a scored run), "stamps": the clock before the first image and after every image}.  evaluate=False
+    stops after the image loop (tools/probe_eval_tail.py times the loop without run_eval's files)."""
     Dataset = get_dataset(opt.dataset, opt.task)
     opt = opts().update_dataset_info_and_set_heads(opt, Dataset)
     dataset = Dataset(opt, "val")
@@ -26,14 +33,47 @@ def test(opt):
     results = {}
     time_stats = ["tot", "load", "pre", "net", "dec", "post", "merge"]
     avg = {t: AverageMeter() for t in time_stats}
-    for ind in range(len(dataset)):
-        img = (synth.uniform("test/img%d" % ind, (opt.input_h, opt.input_w, 3)) * 255).astype(np.uint8)
-        ret = detector.run(img)
-        results[ind] = ret["results"]
+    if opt.dataset == "synthetic":
+        for ind in range(len(dataset)):
+            img = (synth.uniform("test/img%d" % ind, (opt.input_h, opt.input_w, 3)) * 255).astype(np.uint8)
+            ret = detector.run(img)
+            results[ind] = ret["results"]
+            for t in avg:
+                avg[t].update(ret[t])
+            print("[{}/{}] ".format(ind, len(dataset)) + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
+        dataset.run_eval(results, opt.save_dir)
+        return {"ap": None, "results": results, "dataset": dataset, "stamps": []}
+    from centerpoly_amd.datasets import eval_images
+    evaluator = gt_files = None
+    if getattr(opt, "gt_dir", "") and getattr(dataset, "scores_ap", False):
+        from centerpoly_amd.datasets.evaluation import instance_level
+        if not os.path.isdir(opt.gt_dir):
+            raise FileNotFoundError("--gt_dir %s is not a directory" % opt.gt_dir)
+        gt_files = instance_level.find_gt_files(opt.gt_dir)
+        evaluator = instance_level.InstanceLevelEvaluator()
+    images = eval_images.EvalImages(dataset, gt_files)
+    stamps = [time.time()]
+    for ind, item in enumerate(eval_images.iterate(images, not opt.not_prefetch_test, opt.num_workers)):
+        ret = detector.run(item["image"])
+        results[item["img_id"]] = ret["results"]
+        if evaluator is not None:
+            dataset.score_instances_device(detector.device_rows(ret["results"]), item["gt_ids"], item["gt_table"],
+                                           evaluator)
         for t in avg:
             avg[t].update(ret[t])
-        print("[{}/{}] ".format(ind, len(dataset)) + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
-    dataset.run_eval(results, opt.save_dir)
+        print("[{}/{}] ".format(ind, len(images)) + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
+        stamps.append(time.time())
+    if not evaluate:
+        ap = None
+    elif evaluator is None:
+        ap = dataset.run_eval(results, opt.save_dir)
+    else:
+        ap = dataset.finish_scored_eval(results, opt.save_dir, evaluator)
+    return {"ap": ap, "results": results, "dataset": dataset, "stamps": stamps}
+
+
+def test(opt):
+    return run_test(opt)["ap"]
 
 
 if __name__ == "__main__":
