@@ -73,6 +73,8 @@ _SIGNATURES = {
     "cp_color_aug_normalize": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cp_instance_masks": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
     "cp_writer_instances": (c_int32, [_P, c_int32, c_int32, c_float, _P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_class_instance_masks": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
+    "cp_class_writer_instances": (c_int32, [_P, c_int32, c_int32, c_float, c_int32, _P, c_int32] + [_P] * 9),
     "cp_id_histogram": (c_int32, [_P, c_int32, c_int32, _P, _P]),
     "cp_instance_overlaps_workspace_bytes": (c_size_t, [c_int32] * 4),
     "cp_instance_overlaps": (c_int32, [_P, c_int32, _P, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P,

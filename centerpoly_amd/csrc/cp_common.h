@@ -32,3 +32,14 @@ __device__ __forceinline__ double cp_wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+
+// The result writers' vertex, int(float("%.2f" % v)), without text: two decimals round |v| up to the next integer
+// exactly when its fraction is above 0.995 (a float32 fraction is never the tie itself); the sign is kept, as int()
+// truncates towards zero.
+__device__ __forceinline__ int cp_vertex_int(float v) {
+  const double a = fabs((double)v);
+  if (!(a < 2147483520.0)) return a != a ? 0 : (v < 0 ? INT32_MIN : INT32_MAX);   // NaN, infinities, beyond int32
+  const double f = floor(a);
+  const double r = f + ((a - f) > 0.995 ? 1.0 : 0.0);
+  return v < 0 ? -(int)r : (int)r;
+}

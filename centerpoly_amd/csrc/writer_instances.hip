@@ -33,16 +33,6 @@ struct InstArgs {
   unsigned char has_masks[kMaxClasses];
 };
 
-// int(float("%.2f" % v)) without text: two decimals round |v| up to the next integer exactly when its fraction is
-// above 0.995 (a float32 fraction is never the tie itself); the sign is kept, as int() truncates towards zero.
-__device__ __forceinline__ int vertex_int(float v) {
-  const double a = fabs((double)v);
-  if (!(a < 2147483520.0)) return a != a ? 0 : (v < 0 ? INT32_MIN : INT32_MAX);   // NaN, infinities, beyond int32
-  const double f = floor(a);
-  const double r = f + ((a - f) > 0.995 ? 1.0 : 0.0);
-  return v < 0 ? -(int)r : (int)r;
-}
-
 // The three sort keys of a row in one word: the depth as an unsigned number of the same order (-0 and +0 equal, a NaN
 // with +inf), the class, the row.  Keys of different rows differ, so "comes before" is one 64-bit comparison.
 __device__ __forceinline__ unsigned long long sort_key(float depth, int cls, int row) {
@@ -123,7 +113,7 @@ __global__ __launch_bounds__(kMaxRows) void writer_instances_kernel(InstArgs a) 
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const int k = k0 + q * kMaxRows;
-      if (k < total) a.poly[k] = live[q] ? vertex_int(v[q]) : 0;
+      if (k < total) a.poly[k] = live[q] ? cp_vertex_int(v[q]) : 0;
     }
   }
 }

@@ -106,6 +106,18 @@ class PolygonDataset(data.Dataset):
         print("%s: wrote %d detections to %s/results.json" % (self.name, len(dets), save_dir))
         return 0.0
 
+    def report_eval(self, evaluator, res_dir):
+        """The evaluator's table on the screen, its JSON below res_dir; returns allAp."""
+        from ..evaluation import instance_level
+        self.last_evaluator = evaluator
+        res = evaluator.summarize()
+        print(instance_level.format_results(res, evaluator.protocol))
+        out_dir = os.path.join(res_dir, "evaluationResults")
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "resultInstanceLevelSemanticLabeling.json"), "w") as f:
+            json.dump(instance_level.results_json(res, evaluator.protocol), f, indent=4)
+        return res["allAp"]
+
 
 def _to_float(x):
     return float("{:.2f}".format(x))
@@ -289,6 +301,236 @@ class CityscapesWriterMixin(object):
                     Image.fromarray(masks[k]).save(os.path.join(masks_dir, name))
 
 
+class ClassWriterMixin(object):
+    """format_and_write_to_kitti / format_and_write_to_IDD (src/lib/datasets/dataset/kitti_poly.py:95-136,
+    IDD.py:123-170): per image a text file listing `<image>_<k>.png <label id> <score>` and the instance masks as
+    8-bit PNG files on a canvas of the image's own size.  Class by class: a text line per row above the threshold in
+    row order, numbered through the image; the masks drawn in ascending depth within the class as PIL's
+    polygon(outline=0, fill=255), a nearer instance with score >= 0.5 hiding farther ones of ITS class with its fill
+    (PIL draws no outline in the fill's ink, so polygon(outline=0, fill=0) clears the fill alone).  The masks come
+    from cp_class_instance_masks; `ap_protocol` names the evaluator's protocol (evaluation.instance_level.PROTOCOLS),
+    `at_threshold` whether a score equal to the threshold is kept, `per_city` whether the files go into one directory
+    per city (the image's parent directory)."""
+    ap_protocol = None
+    at_threshold = False
+    per_city = False
+
+    def protocol(self):
+        from ..evaluation import instance_level
+        return instance_level.PROTOCOLS[self.ap_protocol]
+
+    def canvas_of(self, image_id):
+        """(width, height) of an image: the annotation record's if it has them, else the image file's header."""
+        im = self.coco.imgs[int(image_id)]
+        if "width" in im and "height" in im:
+            return int(im["width"]), int(im["height"])
+        from PIL import Image
+        file_name = im["file_name"]
+        path = file_name if os.path.isabs(file_name) and os.path.exists(file_name) else \
+            os.path.join(self.img_dir, os.path.basename(file_name))
+        if not os.path.exists(path):
+            raise FileNotFoundError("image %s not found (img_dir %s): its size is the canvas of its masks"
+                                    % (file_name, self.img_dir))
+        with Image.open(path) as img:
+            return img.size
+
+    def image_instances(self, per_class):
+        """The instances of one image in DRAWING order (class, depth, row): (points, score, class index counted
+        from 0, depth, index of the text line).  Scores are compared in float32, as the selection kernel does."""
+        thresh = np.float32(self.opt.thresh)
+        out, count = [], 0
+        for cls_ind in per_class:
+            if cls_ind == "fg":
+                continue
+            params = []
+            for row in per_class[cls_ind]:
+                score = np.float32(row[4])
+                if score >= thresh if self.at_threshold else score > thresh:
+                    poly = [_to_float(v) for v in row[5:-1]]
+                    pts = [(int(x), int(y)) for x, y in zip(poly[0::2], poly[1::2])]
+                    params.append((pts, score, cls_ind - 1, row[-1], count))
+                    count += 1
+            out += sorted(params, key=lambda a: a[3])
+        return out
+
+    def class_label_table(self):
+        """cp_class_writer_instances' table: int32 [C] label id of class 0 .. C-1."""
+        return np.array([self.label_to_id[c] for c in self.class_name[1:]], np.int32)
+
+    def class_masks_device(self, params, canvas, device=None):
+        """Masks of instances in drawing order, left on the device: (uint8 [n, H, W], int32 [n] pixel counts)."""
+        import torch
+
+        from ... import _C
+        W, H = canvas
+        n = len(params)
+        if n == 0:                                           # nothing to draw: no device needed (or touched)
+            return torch.zeros((0, H, W), dtype=torch.uint8), torch.zeros((0,), dtype=torch.int32)
+        dev = device or torch.device("cuda")
+        if n > 128:
+            raise ValueError("more than 128 instances in one image (max_per_image = K <= 128)")
+        N = len(params[0][0])
+        poly = torch.tensor([p[0] for p in params], dtype=torch.int32).reshape(n, N, 2).to(dev)
+        group = torch.tensor([p[2] for p in params], dtype=torch.int32).to(dev)
+        flags = torch.tensor([1 | (2 if p[1] >= 0.5 else 0) for p in params], dtype=torch.uint8).to(dev)
+        masks = torch.empty((n, H, W), dtype=torch.uint8, device=dev)
+        counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        _C.check(_C.lib().cp_class_instance_masks(_C.ptr(poly), _C.ptr(group), _C.ptr(flags), n, N, H, W,
+                                                  _C.ptr(masks), _C.ptr(counts), _C.stream()),
+                 "cp_class_instance_masks")
+        return masks, counts
+
+    def score_instances_device(self, rows_dev, gt_ids, gt_table=None, evaluator=None):
+        """One image scored from its detection rows without a pass through host Python, the KITTI / IDD way: device
+        float32 rows [R, 2N + 7] (x1,y1,x2,y2,score,cls,poly,depth; R <= 1024) -> cp_class_writer_instances ->
+        cp_class_instance_masks -> cp_instance_overlaps on all slots, then ONE read of the small tables.  The canvas
+        is the id image's (an image of another size is refused where both files are known: eval_images, run_eval).
+        gt_ids, gt_table as CityscapesWriterMixin.score_instances_device takes them.  With an `evaluator` the
+        instances are added to it in the order of the text lines.  Returns the tables in that order: n, src, labels,
+        conf (float32), conf_text, counts, text_index, draw_slot, gt_table, inter, void."""
+        import ctypes
+
+        import torch
+
+        from ... import _C
+        from ..evaluation import instance_level as il
+        proto = self.protocol()
+        if rows_dev.dim() != 2 or rows_dev.dtype != torch.float32 or rows_dev.shape[1] < 13 or rows_dev.shape[1] % 2 == 0:
+            raise ValueError("rows must be float32 [R, 2N + 7], got %s %s" % (rows_dev.dtype, tuple(rows_dev.shape)))
+        dev = rows_dev.device
+        R, N = int(rows_dev.shape[0]), (int(rows_dev.shape[1]) - 7) // 2
+        if R == 0:                                                         # no detection at all: one dead row
+            rows_dev = torch.full((1, 2 * N + 7), float("-inf"), dtype=torch.float32, device=dev)
+            R = 1
+        S = min(R, il.MAX_MASKS)                                          # slots drawn and counted
+        if torch.is_tensor(gt_ids):
+            gt_dev = gt_ids
+        else:
+            gt_ids = np.ascontiguousarray(gt_ids)
+            if gt_ids.dtype != np.uint16:
+                raise ValueError("gt_ids must be uint16 (see read_gt_ids), got %s" % gt_ids.dtype)
+            gt_dev = torch.from_numpy(gt_ids.view(np.int16)).to(dev)
+        H, W = (int(v) for v in gt_dev.shape)
+        if gt_table is None:
+            gt_table = il.gt_instances(il.device_histogram(gt_dev), proto)
+        gt_table = np.asarray(gt_table, np.int64).reshape(-1, 3)
+        G = len(gt_table)
+        G0 = min(G, il.MAX_INST)
+        L = _C.lib()
+        table = np.ascontiguousarray(self.class_label_table())
+        ids = torch.from_numpy(np.concatenate([gt_table[:G0, 0], proto.void_ids]).astype(np.int32)).to(dev)
+        fw = (R + 3) // 4
+        # one buffer for everything that comes back: n, then per row src / label / conf / text index / group, per
+        # slot counts / void / pixels, the flag bytes, the intersections
+        o_src, o_lab, o_conf, o_text, o_grp = 4, 4 + R, 4 + 2 * R, 4 + 3 * R, 4 + 4 * R
+        o_cnt = 4 + 5 * R
+        o_void, o_pix, o_flag, o_int = o_cnt + S, o_cnt + 2 * S, o_cnt + 3 * S, o_cnt + 3 * S + fw
+        out = torch.empty((o_int + S * G0,), dtype=torch.int32, device=dev)
+        poly = torch.empty((R, N, 2), dtype=torch.int32, device=dev)
+        masks = torch.empty((S, H, W), dtype=torch.uint8, device=dev)
+        at = lambda o: ctypes.c_void_p(out.data_ptr() + 4 * o)            # noqa: E731
+        st = _C.stream()
+        _C.check(L.cp_class_writer_instances(_C.ptr(rows_dev), R, N, float(self.opt.thresh), int(self.at_threshold),
+                                             table.ctypes.data_as(ctypes.c_void_p), len(table), at(0), at(o_src),
+                                             _C.ptr(poly), at(o_grp), at(o_flag), at(o_lab), at(o_conf), at(o_text),
+                                             st), "cp_class_writer_instances")
+        _C.check(L.cp_class_instance_masks(_C.ptr(poly), at(o_grp), at(o_flag), S, N, H, W, _C.ptr(masks), at(o_cnt),
+                                           st), "cp_class_instance_masks")
+        nbytes = L.cp_instance_overlaps_workspace_bytes(S, G0, H, W)
+        ws = _C.workspace(nbytes, dev)
+        _C.check(L.cp_instance_overlaps(_C.ptr(masks), S, _C.ptr(gt_dev), H, W, _C.ptr(ids), G0,
+                                        ctypes.c_void_p(ids.data_ptr() + 4 * G0), len(proto.void_ids), at(o_int),
+                                        at(o_void), at(o_pix), _C.ptr(ws), nbytes, st), "cp_instance_overlaps")
+        host = out.cpu().numpy()
+        n = int(host[0])
+        if n > il.MAX_MASKS:
+            raise ValueError("more than 128 instances in one image (max_per_image = K <= 128)")
+        inter = host[o_int:o_int + S * G0].reshape(S, G0)[:n].astype(np.int64)
+        for g in range(il.MAX_INST, G, il.MAX_INST):                      # more ids than one call takes: rare
+            more = il.device_counts(masks, gt_dev, gt_table[g:g + il.MAX_INST, 0], proto)[0]
+            inter = np.concatenate([inter, more[:n]], axis=1)
+        text = host[o_text:o_text + n]
+        order = np.argsort(text, kind="stable")                           # slot of text line 0, 1, ...
+        conf = host[o_conf:o_conf + n].view(np.float32)[order]
+        res = {"n": n, "src": host[o_src:o_src + n][order], "labels": host[o_lab:o_lab + n][order].astype(np.int64),
+               "conf": conf.copy(), "conf_text": [str(c) for c in conf],
+               "counts": host[o_cnt:o_cnt + n][order].astype(np.int64), "text_index": text[order].copy(),
+               "draw_slot": order, "gt_table": gt_table, "inter": inter[order],
+               "void": host[o_void:o_void + n][order].astype(np.int64)}
+        if evaluator is not None:
+            pix = host[o_pix:o_pix + n][order].astype(np.int64)
+            evaluator.add_counts(gt_table, res["labels"].tolist(), [float(c) for c in res["conf_text"]], pix,
+                                 res["void"], res["inter"])
+        return res
+
+    def format_and_write_class_masks(self, all_bboxes, save_dir, evaluator=None, gt_files=None, write_files=True):
+        """Writes the result files; with an `evaluator` the masks are also scored against `gt_files` ({image key:
+        id image path}) while they are on the device."""
+        from PIL import Image
+        proto = self.protocol()
+        for image_id in all_bboxes:
+            file_name = self.coco.imgs[int(image_id)]["file_name"]
+            base = os.path.basename(file_name)
+            params = self.image_instances(all_bboxes[image_id])
+            canvas = self.canvas_of(image_id)
+            masks_dev, _ = self.class_masks_device(params, canvas)
+            by_line = sorted(range(len(params)), key=lambda k: params[k][4])
+            labels = [int(self.label_to_id[self.class_name[params[k][2] + 1]]) for k in by_line]
+            confs = [str(params[k][1]) for k in by_line]
+            if evaluator is not None:
+                from ..evaluation import instance_level
+                key = proto.image_key(file_name)
+                if key not in gt_files:
+                    raise FileNotFoundError("no ground truth %s below --gt_dir for image %s" % (proto.gt_name(key), base))
+                gt_ids = instance_level.read_gt_ids(gt_files[key])
+                if gt_ids.shape != (canvas[1], canvas[0]):
+                    raise ValueError("%s is %s, the image %s is %s" % (gt_files[key], gt_ids.shape, file_name,
+                                                                       (canvas[1], canvas[0])))
+                evaluator.add_image(masks_dev[by_line] if len(params) else masks_dev, labels, [float(c) for c in confs],
+                                    gt_ids)
+            if not write_files:
+                continue
+            write_dir = os.path.join(save_dir, os.path.basename(os.path.dirname(file_name))) if self.per_city else save_dir
+            os.makedirs(write_dir, exist_ok=True)
+            masks = masks_dev.cpu().numpy()
+            with open(os.path.join(write_dir, base.replace(".png", ".txt")), "w") as text_file:
+                for count, (k, lab, conf) in enumerate(zip(by_line, labels, confs)):
+                    name = base.replace(".png", "_" + str(count) + ".png")
+                    text_file.write(name + " " + str(lab) + " " + conf + "\n")
+                    Image.fromarray(masks[k]).save(os.path.join(write_dir, name))
+
+    def run_eval(self, results, save_dir):
+        """kitti_poly.py / IDD.py run_eval: results.json + the per-image mask files their instance-level evaluation
+        reads.  With --gt_dir the masks are also scored on the device (evaluation/instance_level.py, this data set's
+        protocol), the evaluator's table is printed, its JSON written and allAp returned; --no_mask_files then skips
+        the mask and text files.  Without --gt_dir nothing is scored and the return value is 0.0."""
+        PolygonDataset.run_eval(self, results, save_dir)
+        res_dir = os.path.join(save_dir, "results")
+        os.makedirs(res_dir, exist_ok=True)
+        gt_dir = getattr(self.opt, "gt_dir", "")
+        if not gt_dir:
+            self.format_and_write_class_masks(results, res_dir)
+            return 0.0
+        from ..evaluation import instance_level
+        if not os.path.isdir(gt_dir):
+            raise FileNotFoundError("--gt_dir %s is not a directory" % gt_dir)
+        evaluator = instance_level.InstanceLevelEvaluator(self.protocol())
+        self.format_and_write_class_masks(results, res_dir, evaluator,
+                                          instance_level.find_gt_files(gt_dir, self.protocol()),
+                                          write_files=not getattr(self.opt, "no_mask_files", False))
+        return self.report_eval(evaluator, res_dir)
+
+    def finish_scored_eval(self, results, save_dir, evaluator):
+        """run_eval for a run whose images were already scored as they passed (score_instances_device with
+        `evaluator`): results.json, the mask and text files unless --no_mask_files, the report."""
+        PolygonDataset.run_eval(self, results, save_dir)
+        res_dir = os.path.join(save_dir, "results")
+        os.makedirs(res_dir, exist_ok=True)
+        if not getattr(self.opt, "no_mask_files", False):
+            self.format_and_write_class_masks(results, res_dir)
+        return self.report_eval(evaluator, res_dir)
+
+
 class CITYSCAPES(CityscapesWriterMixin, PolygonDataset):
     """src/lib/datasets/dataset/cityscapes.py:39-110."""
     name = "cityscapes"
@@ -331,18 +573,6 @@ class CITYSCAPES(CityscapesWriterMixin, PolygonDataset):
                                             write_files=not getattr(self.opt, "no_mask_files", False))
         return self.report_eval(evaluator, res_dir)
 
-    def report_eval(self, evaluator, res_dir):
-        """The evaluator's table on the screen, its JSON below res_dir; returns allAp."""
-        from ..evaluation import instance_level
-        self.last_evaluator = evaluator
-        res = evaluator.summarize()
-        print(instance_level.format_results(res))
-        out_dir = os.path.join(res_dir, "evaluationResults")
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, "resultInstanceLevelSemanticLabeling.json"), "w") as f:
-            json.dump(instance_level.results_json(res), f, indent=4)
-        return res["allAp"]
-
     def finish_scored_eval(self, results, save_dir, evaluator):
         """run_eval for a run whose images were already scored as they passed (score_instances_device with
         `evaluator`): results.json, the mask and text files through the writer unless --no_mask_files, the report."""
@@ -354,9 +584,13 @@ class CITYSCAPES(CityscapesWriterMixin, PolygonDataset):
         return self.report_eval(evaluator, res_dir)
 
 
-class KITTIPOLY(PolygonDataset):
-    """src/lib/datasets/dataset/kitti_poly.py:15-60."""
+class KITTIPOLY(ClassWriterMixin, PolygonDataset):
+    """src/lib/datasets/dataset/kitti_poly.py:15-60; its writer keeps a row when score > thresh."""
     name = "kitti_poly"
+    label_to_id = {"person": 24, "rider": 25, "car": 26, "truck": 27, "bus": 28, "train": 31, "motorcycle": 32,
+                   "bicycle": 33}
+    ap_protocol = "kitti"                                    # test.py / run_eval score with --gt_dir (scores_ap stays
+    at_threshold = False                                     # False: `main.py --metric ap` is still refused here)
     annot_subdir = os.path.join("KITTIPolyStuff", "BBoxes")
     mean = np.array([0.485, 0.456, 0.406], np.float32).reshape(1, 1, 3)
     std = np.array([0.229, 0.224, 0.225], np.float32).reshape(1, 1, 3)
@@ -369,9 +603,15 @@ class KITTIPOLY(PolygonDataset):
         return "%s%d.json" % ("val" if split == "val" else "train", self.opt.nbr_points)
 
 
-class IDD(PolygonDataset):
-    """src/lib/datasets/dataset/IDD.py:15-60 (9 classes, the Cityscapes statistics)."""
+class IDD(ClassWriterMixin, PolygonDataset):
+    """src/lib/datasets/dataset/IDD.py:15-60 (9 classes, the Cityscapes statistics); its writer keeps a row when
+    score >= thresh and writes one directory per city."""
     name = "IDD"
+    label_to_id = {"person": 6, "rider": 8, "motorcycle": 9, "bicycle": 10, "autorickshaw": 11, "car": 12,
+                   "truck": 13, "bus": 14, "vehicle fallback": 18}
+    ap_protocol = "IDD"
+    at_threshold = True
+    per_city = True
     num_classes = 9
     annot_subdir = os.path.join("IDDStuff", "BBoxes")
     mean = CITYSCAPES.mean

@@ -13,14 +13,14 @@ from .evaluation import instance_level
 
 def image_prefix(file_name):
     """`frankfurt_000000_000294` of `.../frankfurt_000000_000294_leftImg8bit.png`: the key of the ground truth."""
-    base = os.path.basename(file_name)
-    return base[:-len("_leftImg8bit.png")] if base.endswith("_leftImg8bit.png") else os.path.splitext(base)[0]
+    return instance_level.CITYSCAPES.image_key(file_name)
 
 
 class EvalImages(data.Dataset):
-    def __init__(self, dataset, gt_files=None):
+    def __init__(self, dataset, gt_files=None, protocol=None):
         self.dataset = dataset
-        self.gt_files = gt_files                               # {image prefix: id image path} or None
+        self.gt_files = gt_files                               # {image key: id image path} or None
+        self.protocol = protocol or instance_level.CITYSCAPES  # whose key, ground-truth table and file names
 
     def __len__(self):
         return len(self.dataset.images)
@@ -31,11 +31,11 @@ class EvalImages(data.Dataset):
         return img_id, self.dataset.coco.loadImgs(ids=[img_id])[0]["file_name"]
 
     def gt_path(self, file_name):
-        prefix = image_prefix(file_name)
-        if prefix not in self.gt_files:
-            raise FileNotFoundError("no ground truth %s%s below --gt_dir for image %s"
-                                    % (prefix, instance_level.GT_SUFFIX, os.path.basename(file_name)))
-        return self.gt_files[prefix]
+        key = self.protocol.image_key(file_name)
+        if key not in self.gt_files:
+            raise FileNotFoundError("no ground truth %s below --gt_dir for image %s"
+                                    % (self.protocol.gt_name(key), os.path.basename(file_name)))
+        return self.gt_files[key]
 
     def __getitem__(self, ind):
         img_id, file_name = self.info(ind)
@@ -45,8 +45,12 @@ class EvalImages(data.Dataset):
             if not os.path.isfile(path):
                 raise FileNotFoundError("ground truth %s not found" % path)
             ids = instance_level.read_gt_ids(path)
+            if self.protocol is not instance_level.CITYSCAPES and ids.shape != item["image"].shape[:2]:
+                raise ValueError("%s is %s, the image %s is %s: KITTI / IDD masks are drawn on the image's own canvas"
+                                 % (path, ids.shape, file_name, item["image"].shape[:2]))
             item["gt_ids"] = ids
-            item["gt_table"] = instance_level.gt_instances(np.bincount(ids.reshape(-1), minlength=65536))
+            item["gt_table"] = instance_level.gt_instances(np.bincount(ids.reshape(-1), minlength=65536),
+                                                           self.protocol)
         return item
 
 

@@ -1,4 +1,4 @@
-"""Cityscapes instance-level AP (the protocol of cityscapesscripts' evalInstanceLevelSemanticLabeling, the
+"""Instance-level AP of Cityscapes, KITTI and IDD (the protocol of cityscapesscripts' evalInstanceLevelSemanticLabeling, the
 `distanceAvailable = False` case the reference runs after test.py), written from the algorithm.
 
 The pixel work -- one count per (predicted mask, ground-truth instance) pair, the void overlap, the mask sizes and
@@ -33,13 +33,77 @@ GT_SUFFIX = "_gtFine_instanceIds.png"
 MAX_MASKS, MAX_INST = 128, 1024                          # limits of cp_instance_overlaps
 
 
-def gt_instances(hist):
+class Protocol(object):
+    """What the three evaluators of the reference (cityscapesscripts, kittiscripts, IDDscripts) do NOT share; the
+    matching and the AP are the same protocol.
+      inst_labels / label_ids   the labels with instances, in the evaluator's order
+      void_ids                  raw pixel values of the labels its table marks ignoreInEval
+      label_of(ids)             label id of an array of instance ids
+      gt_filter(ids)            which ids enter the ground-truth table at all (before the label test)
+      gt_key(dir, file)         key of a ground-truth file below --gt_dir, None for any other file
+      image_key(file_name)      the same key from an image's file name
+      pred_match(path, key)     whether the text file at `path` (below the result directory) is the image's
+      gt_name(key)              how a missing ground-truth file is named in an error"""
+
+    def __init__(self, name, inst_labels, label_ids, void_ids, label_of, gt_filter, gt_key, image_key, pred_match,
+                 gt_name):
+        self.name, self.inst_labels = name, tuple(inst_labels)
+        self.label_ids, self.void_ids = tuple(label_ids), tuple(void_ids)
+        self.label_of, self.gt_filter, self.gt_key, self.image_key = label_of, gt_filter, gt_key, image_key
+        self.pred_match, self.gt_name = pred_match, gt_name
+
+
+def _thousands(ids):
+    return np.where(ids < 1000, ids, ids // 1000)
+
+
+def _every(ids):
+    return np.ones(ids.shape, bool)
+
+
+def _suffix_key(suffix):
+    return lambda root, f: f[:-len(suffix)] if f.endswith(suffix) else None
+
+
+def _image_prefix(file_name):
+    base = os.path.basename(file_name)
+    return base[:-len("_leftImg8bit.png")] if base.endswith("_leftImg8bit.png") else os.path.splitext(base)[0]
+
+
+def _idd_gt_key(root, f):
+    return os.path.basename(root) + "/" + f.split("_")[0] if f.endswith(IDD_GT_SUFFIX) else None
+
+
+def _idd_image_key(file_name):
+    return os.path.basename(os.path.dirname(file_name)) + "/" + os.path.basename(file_name).split("_")[0]
+
+
+IDD_GT_SUFFIX = "_gtFine_instanceids.png"                # lower-case `ids`, one directory per city
+CITYSCAPES = Protocol("cityscapes", INST_LABELS, LABEL_IDS, VOID_IDS, _thousands, _every, _suffix_key(GT_SUFFIX),
+                      _image_prefix, lambda path, key: fnmatch.fnmatch(os.path.basename(path), key + "*.txt"),
+                      lambda key: key + GT_SUFFIX)
+# kittiscripts: Cityscapes' label table, ids are label * 256 + k, the ground truth is `<image base name>.png`
+KITTI = Protocol("kitti", INST_LABELS, LABEL_IDS, VOID_IDS, lambda ids: ids // 256, _every,
+                 lambda root, f: f[:-4] if f.endswith(".png") else None,
+                 lambda file_name: os.path.splitext(os.path.basename(file_name))[0],
+                 lambda path, key: os.path.basename(path) == key + ".txt", lambda key: key + ".png")
+# IDDscripts: the anue label table (levels of 1000 as in Cityscapes); instances2dict lets an id in only when it is
+# not 255 and its thousands are a label between 6 and 18, so there are no group ids in its tables
+IDD = Protocol("IDD", ("person", "rider", "motorcycle", "bicycle", "autorickshaw", "car", "truck", "bus",
+                       "vehicle fallback"), (6, 8, 9, 10, 11, 12, 13, 14, 18),
+               (7, 15, 16, 17, 35, 36, 37, 38, 39), _thousands,
+               lambda ids: (ids != 255) & (ids // 1000 > 5) & (ids // 1000 < 19), _idd_gt_key, _idd_image_key,
+               lambda path, key: fnmatch.fnmatch("/" + path, "*/" + key + "*.txt"), lambda key: key + IDD_GT_SUFFIX)
+PROTOCOLS = {"cityscapes": CITYSCAPES, "kitti": KITTI, "IDD": IDD}
+
+
+def gt_instances(hist, protocol=CITYSCAPES):
     """The ground-truth table of one image from its id histogram (int [65536]): int64 [G, 3] rows
-    (instID, labelID, pixelCount) of the ids whose label is one of the eight, ascending instID."""
+    (instID, labelID, pixelCount) of the ids the protocol lets in whose label has instances, ascending instID."""
     hist = np.asarray(hist)
     ids = np.flatnonzero(hist)
-    labels = np.where(ids < 1000, ids, ids // 1000)
-    keep = np.isin(labels, LABEL_IDS)
+    labels = protocol.label_of(ids)
+    keep = np.isin(labels, protocol.label_ids) & protocol.gt_filter(ids)
     return np.stack([ids[keep], labels[keep], hist[ids[keep]]], 1).astype(np.int64).reshape(-1, 3)
 
 
@@ -54,19 +118,22 @@ def read_gt_ids(path):
     return np.ascontiguousarray(arr.astype(np.uint16))
 
 
-def find_gt_files(gt_dir):
-    """{image prefix: path} of every *_gtFine_instanceIds.png below gt_dir."""
+def find_gt_files(gt_dir, protocol=CITYSCAPES):
+    """{image key: path} of every ground-truth file below gt_dir (Cityscapes: *_gtFine_instanceIds.png by image
+    prefix; KITTI: *.png by base name; IDD: <city>/<frame>_gtFine_instanceids.png by `<city>/<frame>`)."""
     out = {}
     for root, _, files in os.walk(gt_dir):
-        for f in fnmatch.filter(files, "*" + GT_SUFFIX):
-            key = f[:-len(GT_SUFFIX)]
+        for f in sorted(files):
+            key = protocol.gt_key(root, f)
+            if key is None:
+                continue
             if key in out:
                 raise ValueError("two ground-truth files for %s: %s and %s" % (key, out[key], os.path.join(root, f)))
             out[key] = os.path.join(root, f)
     return out
 
 
-def device_counts(masks_dev, gt_dev, inst_ids):
+def device_counts(masks_dev, gt_dev, inst_ids, protocol=CITYSCAPES):
     """cp_instance_overlaps on device masks uint8 [n, H, W] and device ids [H, W] (16-bit elements):
     (inter [n, G], void_inter [n], pred_pixels [n]) as host int64 arrays."""
     import torch
@@ -76,13 +143,13 @@ def device_counts(masks_dev, gt_dev, inst_ids):
     G = len(inst_ids)
     dev = masks_dev.device
     inst = torch.tensor(list(inst_ids), dtype=torch.int32).to(dev)
-    void = torch.tensor(VOID_IDS, dtype=torch.int32).to(dev)
+    void = torch.tensor(protocol.void_ids, dtype=torch.int32).to(dev)
     out = torch.empty((n * G + 2 * n,), dtype=torch.int32, device=dev)
     L = _C.lib()
     nbytes = L.cp_instance_overlaps_workspace_bytes(n, G, H, W)
     ws = _C.workspace(nbytes, dev)
     _C.check(L.cp_instance_overlaps(_C.ptr(masks_dev), n, _C.ptr(gt_dev), H, W, _C.ptr(inst), G, _C.ptr(void),
-                                    len(VOID_IDS), _C.ptr(out[:n * G]), _C.ptr(out[n * G:n * G + n]),
+                                    len(protocol.void_ids), _C.ptr(out[:n * G]), _C.ptr(out[n * G:n * G + n]),
                                     _C.ptr(out[n * G + n:]), _C.ptr(ws), nbytes, _C.stream()), "cp_instance_overlaps")
     host = out.cpu().numpy().astype(np.int64)
     return host[:n * G].reshape(n, G), host[n * G:n * G + n], host[n * G + n:]
@@ -102,18 +169,20 @@ def device_histogram(gt_dev):
 class InstanceLevelEvaluator(object):
     """Collects the count tables image by image (add_image / add_counts) and scores them (summarize)."""
 
-    def __init__(self):
+    def __init__(self, protocol=CITYSCAPES):
+        self.protocol = protocol
         self.images = []
 
     def add_counts(self, gt_table, label_ids, confidences, pred_pixels, void_inter, inter):
         """One image from its counts: gt_table [G, 3] as gt_instances returns it; per prediction its label id,
         confidence, pixel count and void overlap; inter [n, G], column j counted against gt_table[j].  Predictions
-        with a label outside the eight or without pixels are skipped, as the protocol skips them."""
+        with a label without instances or without pixels are skipped, as the protocol skips them.  The order of
+        the predictions is the order of the text file's lines: the scores are sorted stably, so it can show in an AP."""
         gt_table = np.asarray(gt_table, np.int64).reshape(-1, 3)
         inter = np.asarray(inter, np.int64).reshape(len(label_ids), len(gt_table))
         preds = []
         for i, (lab, conf) in enumerate(zip(label_ids, confidences)):
-            if int(lab) not in LABEL_IDS or int(pred_pixels[i]) == 0:
+            if int(lab) not in self.protocol.label_ids or int(pred_pixels[i]) == 0:
                 continue
             preds.append((int(lab), float(conf), int(pred_pixels[i]), int(void_inter[i]), inter[i]))
         self.images.append((gt_table, preds))
@@ -133,22 +202,22 @@ class InstanceLevelEvaluator(object):
             raise ValueError("%d masks, %d labels, %d confidences" % (n, len(label_ids), len(confidences)))
         if tuple(masks_dev.shape[1:]) != tuple(gt_ids.shape):
             raise ValueError("masks are %s, the id image is %s" % (tuple(masks_dev.shape[1:]), tuple(gt_ids.shape)))
-        table = gt_instances(device_histogram(gt_ids))
+        table = gt_instances(device_histogram(gt_ids), self.protocol)
         G = len(table)
         inter = np.zeros((n, G), np.int64)
         void = np.zeros((n,), np.int64)
         pix = np.zeros((n,), np.int64)
         for a in range(0, n, MAX_MASKS):
             for g in range(0, max(G, 1), MAX_INST):
-                i, v, p = device_counts(masks_dev[a:a + MAX_MASKS], gt_ids, table[g:g + MAX_INST, 0])
+                i, v, p = device_counts(masks_dev[a:a + MAX_MASKS], gt_ids, table[g:g + MAX_INST, 0], self.protocol)
                 inter[a:a + MAX_MASKS, g:g + MAX_INST], void[a:a + MAX_MASKS], pix[a:a + MAX_MASKS] = i, v, p
         self.add_counts(table, label_ids, confidences, pix, void, inter)
 
     def ap_matrix(self):
-        """float64 [1, 8, 10]: AP per (region size setting, class, overlap threshold)."""
-        ap = np.zeros((1, len(LABEL_IDS), len(OVERLAPS)), np.float64)
+        """float64 [1, labels, 10]: AP per (region size setting, class, overlap threshold)."""
+        ap = np.zeros((1, len(self.protocol.label_ids), len(OVERLAPS)), np.float64)
         for oi, th in enumerate(OVERLAPS):
-            for li, lab in enumerate(LABEL_IDS):
+            for li, lab in enumerate(self.protocol.label_ids):
                 ap[0, li, oi] = self._class_ap(lab, th)
         return ap
 
@@ -213,23 +282,23 @@ class InstanceLevelEvaluator(object):
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)             # no ground truth at all: nan, not a warning
             res = {"allAp": float(np.nanmean(ap[0])), "allAp50%": float(np.nanmean(ap[0, :, 0])), "classes": {}}
-        for li, name in enumerate(INST_LABELS):
+        for li, name in enumerate(self.protocol.inst_labels):
             res["classes"][name] = {"ap": float(np.average(ap[0, li])), "ap50%": float(ap[0, li, 0])}
         res["resultApMatrix"] = ap
         return res
 
 
-def results_json(res):
+def results_json(res, protocol=CITYSCAPES):
     """The dictionary the evaluator writes as resultInstanceLevelSemanticLabeling.json."""
     return {"averages": {k: v for k, v in res.items() if k != "resultApMatrix"}, "overlaps": OVERLAPS.tolist(),
-            "minRegionSizes": MIN_REGION_SIZES.tolist(), "instLabels": list(INST_LABELS),
+            "minRegionSizes": MIN_REGION_SIZES.tolist(), "instLabels": list(protocol.inst_labels),
             "resultApMatrix": res["resultApMatrix"].tolist()}
 
 
-def format_results(res):
+def format_results(res, protocol=CITYSCAPES):
     """The evaluator's result table as text."""
     lines = ["", "#" * 50, "{:<15}".format("what") + ":" + "{:>15}".format("AP") + "{:>15}".format("AP_50%"), "#" * 50]
-    for name in INST_LABELS:
+    for name in protocol.inst_labels:
         c = res["classes"][name]
         lines.append("{:<15}".format(name) + ":" + "{:>15.3f}".format(c["ap"]) + "{:>15.3f}".format(c["ap50%"]))
     lines += ["-" * 50, "{:<15}".format("average") + ":" + "{:>15.3f}".format(res["allAp"])
@@ -251,24 +320,27 @@ def read_pred_info(txt_path):
     return out
 
 
-def evaluate_result_dir(pred_dir, gt_files, device=None):
-    """Scores a result directory in the Cityscapes layout (`<image>*.txt` listing `masks/*.png`, searched below
-    pred_dir by the prefix of each ground-truth file).  Masks are uploaded image by image."""
+def evaluate_result_dir(pred_dir, gt_files, device=None, protocol=CITYSCAPES):
+    """Scores a result directory in the protocol's layout (Cityscapes: `<image>*.txt` listing `masks/*.png`; KITTI:
+    `<base name>.txt`; IDD: `<city>/<frame>*.txt`, both with the masks next to the text file), searched below pred_dir
+    by the key of each ground-truth file.  Masks are uploaded image by image."""
     import torch
     from PIL import Image
     dev = device or torch.device("cuda")
     txts = [os.path.join(r, f) for r, _, files in os.walk(pred_dir) for f in files if f.endswith(".txt")]
-    ev = InstanceLevelEvaluator()
+    ev = InstanceLevelEvaluator(protocol)
     for gt in gt_files:
-        base = os.path.basename(gt)
-        prefix = base[:-len(GT_SUFFIX)] if base.endswith(GT_SUFFIX) else os.path.splitext(base)[0]
-        mine = [t for t in txts if fnmatch.fnmatch(os.path.basename(t), prefix + "*.txt")]
+        root, base = os.path.split(gt)
+        key = protocol.gt_key(root, base)
+        if key is None:
+            key = os.path.splitext(base)[0]
+        mine = [t for t in txts if protocol.pred_match(os.path.relpath(t, pred_dir).replace(os.sep, "/"), key)]
         if len(mine) != 1:
-            raise FileNotFoundError("%d prediction files %s*.txt below %s for ground truth %s"
-                                    % (len(mine), prefix, pred_dir, gt))
+            raise FileNotFoundError("%d prediction text files for %s below %s (ground truth %s)"
+                                    % (len(mine), key, pred_dir, gt))
         ids = read_gt_ids(gt)
         info = read_pred_info(mine[0])
-        info = [p for p in info if p[1] in LABEL_IDS]                      # other labels are never opened
+        info = [p for p in info if p[1] in protocol.label_ids]                      # other labels are never opened
         masks = np.zeros((len(info),) + ids.shape, np.uint8)
         for k, (path, _, _) in enumerate(info):
             m = np.array(Image.open(path).convert("L"))

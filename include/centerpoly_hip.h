@@ -50,7 +50,8 @@ extern "C" {
 
 #define CP_ABI_VERSION 3   /* 3 (round 4): + cp_polydet_decode_ex, cp_dense_l1_*, cp_polydet_dense_targets, cp_conv_direct_forward_ex,
                               cp_conv_mfma_forward_split, cp_activation_split / _unsplit, cp_dla_base_pair_*; no signature changed.
-                              Added since, backward compatible (no version change): cp_polydet_targets_ex */
+                              Added since, backward compatible (no version change): cp_polydet_targets_ex,
+                              cp_class_instance_masks, cp_class_writer_instances */
 
 enum {
   CP_OK = 0,
@@ -436,6 +437,44 @@ int cp_instance_overlaps(const uint8_t* masks, int32_t n, const uint16_t* gt_ids
 int cp_writer_instances(const float* rows, int32_t R, int32_t N, float thresh, const int32_t* class_table, int32_t C,
                         int32_t* n_out, int32_t* src, int32_t* poly, uint8_t* flags, int32_t* label, float* conf,
                         void* stream);
+
+/* ------------------------------------------------ KITTI / IDD result writers --
+ * cp_class_instance_masks: the per-instance drawing of format_and_write_to_kitti / format_and_write_to_IDD
+ * (src/lib/datasets/dataset/kitti_poly.py:126-136, IDD.py:160-170) for the instances of ONE image in drawing order
+ * (ascending depth within a group): with F what ImageDraw.polygon(pts, fill=...) sets and O what
+ * ImageDraw.polygon(pts, outline=...) sets in PIL 12.2 on an 'L' image,
+ *   mask_i = (F_i \ O_i) \ union { F_j : j < i, group_j == group_i, flags_j bit 1 set }
+ * (the writers clear to_remove_mask with polygon(outline=0, fill=0), and PIL draws no outline in the fill's ink).
+ *   poly   DEVICE int32 [n][N][2]  integer (x, y) vertices      group  DEVICE int32 [n], compared for equality (the
+ *   class); the instances of a group need not be adjacent       flags  DEVICE uint8 [n]: bit 0 = draw (0: the mask
+ *   is empty and hides nothing), bit 1 = score >= 0.5 (hides farther instances of its group)
+ *   masks  DEVICE uint8 [n][H][W] out, 0 / 255, any alignment   counts DEVICE int32 [n] out, non-zero pixels
+ * n <= 128, 3 <= N <= 64, H * W < 2^31 (CP_EUNSUPPORTED beyond), any H and W; all checks come before any device
+ * work.  F and O are PIL's scan-line fill and integer line restated (csrc/class_masks_core.h), exact for vertices
+ * within +-2^24; farther out nothing is written outside the canvas but the drawing is not PIL's.  A fixed number of
+ * launches whatever n is; integer results, the same bits on every run. */
+int cp_class_instance_masks(const int32_t* poly, const int32_t* group, const uint8_t* flags, int32_t n, int32_t N,
+                            int32_t H, int32_t W, uint8_t* masks, int32_t* counts, void* stream);
+
+/* cp_class_writer_instances: the selection of those two writers for ONE image on the device, from detection rows in
+ * the layout cp_polydet_post_process writes to the instance list cp_class_instance_masks and the evaluator read.
+ *   rows   DEVICE fp32 [R][2N + 7]: x1,y1,x2,y2,score,cls,poly(2N),depth (cls counts from 0)
+ *   at_threshold  0: a row is live when score > thresh (KITTI), 1: when score >= thresh (IDD); fp32
+ *   class_label   HOST int32 [C]: label id of class 0 .. C-1
+ *   n_out  DEVICE int32 [1]: live instances        src    DEVICE int32 [R]: source row of every instance
+ *   poly   DEVICE int32 [R][N][2]                  group  DEVICE int32 [R]: the class
+ *   flags  DEVICE uint8 [R]: 1 | (score >= 0.5 ? 2 : 0)         label  DEVICE int32 [R]
+ *   conf   DEVICE fp32 [R]: the score as it is     text_index DEVICE int32 [R]: the writers' `count`, the line of
+ *   the instance in the image's text file = its place in the order (class, row)
+ * Instances are in DRAWING order: class, then ascending depth, ties by row (the stable sort of the host loop; a NaN
+ * depth sorts last).  Vertices as cp_writer_instances has them.  Slots at n_out and above are dead: flags 0, src,
+ * group, label and text_index -1, conf 0, vertices 0.  More than 128 live rows are reported through n_out.
+ * 1 <= R <= 1024, 3 <= N <= 64, 1 <= C <= 32: beyond the upper limits CP_EUNSUPPORTED, otherwise (null pointers, a
+ * NaN threshold, at_threshold not 0 or 1) CP_EINVAL, all before any device work.  One launch of one workgroup. */
+int cp_class_writer_instances(const float* rows, int32_t R, int32_t N, float thresh, int32_t at_threshold,
+                              const int32_t* class_label, int32_t C, int32_t* n_out, int32_t* src, int32_t* poly,
+                              int32_t* group, uint8_t* flags, int32_t* label, float* conf, int32_t* text_index,
+                              void* stream);
 
 /* ------------------------------------------------ detector pre/post-processing --
  * cp_preprocess_warp_normalize: the cv2 stage of BaseDetector.pre_process

@@ -2,9 +2,10 @@
 """Evaluation driver with the reference's CLI and control flow (src/test.py:47-131):
 `python test.py polydet --arch dla_34 --load_model model_last.pth`.  `cityscapes`, `kitti_poly` and `IDD` read their
 image files (`dataset.images` -> `coco.loadImgs` -> `read_image`), by default through a prefetching DataLoader whose
-workers decode ahead of the detector, with --not_prefetch_test in a plain loop.  With --gt_dir on Cityscapes every
-image is scored on the device as it passes (CityscapesWriterMixin.score_instances_device) and the instance-level allAp
-is returned.  `--dataset synthetic` feeds hash-generated uint8 arrays (no files)."""
+workers decode ahead of the detector, with --not_prefetch_test in a plain loop.  With --gt_dir every image is scored on
+the device as it passes (score_instances_device of the data set's writer: Cityscapes, or KITTI / IDD by their own
+evaluators' protocols) and the instance-level allAp is returned.  `--dataset synthetic` feeds hash-generated uint8
+arrays (no files)."""
 import os
 import sys
 import time
@@ -44,14 +45,15 @@ def run_test(opt, evaluate=True):
         dataset.run_eval(results, opt.save_dir)
         return {"ap": None, "results": results, "dataset": dataset, "stamps": []}
     from centerpoly_amd.datasets import eval_images
-    evaluator = gt_files = None
-    if getattr(opt, "gt_dir", "") and getattr(dataset, "scores_ap", False):
+    evaluator = gt_files = protocol = None
+    if getattr(opt, "gt_dir", "") and (getattr(dataset, "scores_ap", False) or getattr(dataset, "ap_protocol", None)):
         from centerpoly_amd.datasets.evaluation import instance_level
         if not os.path.isdir(opt.gt_dir):
             raise FileNotFoundError("--gt_dir %s is not a directory" % opt.gt_dir)
-        gt_files = instance_level.find_gt_files(opt.gt_dir)
-        evaluator = instance_level.InstanceLevelEvaluator()
-    images = eval_images.EvalImages(dataset, gt_files)
+        protocol = instance_level.PROTOCOLS[getattr(dataset, "ap_protocol", None) or "cityscapes"]
+        gt_files = instance_level.find_gt_files(opt.gt_dir, protocol)
+        evaluator = instance_level.InstanceLevelEvaluator(protocol)
+    images = eval_images.EvalImages(dataset, gt_files, protocol)
     stamps = [time.time()]
     for ind, item in enumerate(eval_images.iterate(images, not opt.not_prefetch_test, opt.num_workers)):
         ret = detector.run(item["image"])
