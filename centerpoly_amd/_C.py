@@ -30,6 +30,13 @@ class TargetShape(Structure):
                                        "rep", "no_reorder_flip")]
 
 
+class OverlayParams(Structure):
+    """cp_overlay_params of include/centerpoly_hip.h."""
+    _fields_ = [(n, c_int32) for n in ("alpha", "outline_radius", "box_thickness", "white_theme", "show_txt",
+                                       "show_polygons")] + \
+               [("outline_colour", ctypes.c_uint8 * 3), ("reserved", ctypes.c_uint8)]
+
+
 class NativeLibraryMissing(ImportError):
     pass
 
@@ -75,6 +82,10 @@ _SIGNATURES = {
     "cp_writer_instances": (c_int32, [_P, c_int32, c_int32, c_float, _P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "cp_class_instance_masks": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
     "cp_class_writer_instances": (c_int32, [_P, c_int32, c_int32, c_float, c_int32, _P, c_int32] + [_P] * 9),
+    "cp_render_overlay_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "cp_render_overlay": (c_int32, [_P, c_int32, c_int32, _P, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, c_int32, _P,
+                                    c_int32, _P, _P, _P, c_size_t, _P]),
+    "cp_render_heatmap": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P]),
     "cp_id_histogram": (c_int32, [_P, c_int32, c_int32, _P, _P]),
     "cp_instance_overlaps_workspace_bytes": (c_size_t, [c_int32] * 4),
     "cp_instance_overlaps": (c_int32, [_P, c_int32, _P, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P,

@@ -7,8 +7,14 @@ running on the host.  cv2 is not required: the 8-bit image is uploaded as is and
 the affine warp + normalisation of pre_process run in one HIP kernel with OpenCV's
 fixed-point arithmetic (cp_preprocess_warp_normalize), a .npy path or ndarray is
 accepted as the image source, and `opt.load_model == ''` keeps the random
-initialisation (the reference calls torch.load unconditionally, :27).
+initialisation (the reference calls torch.load unconditionally, :27).  An image file
+path is read through PIL into cv2.imread's layout (8-bit BGR).
+
+--debug >= 1 (reference :108-109, 145-146, 186-187): run() draws the detections on the
+device (utils/debugger.py), writes the pictures into opt.debug_dir and returns the
+overlay as ret['vis']; at --debug 0 no Debugger exists and nothing else changes.
 """
+import os
 import time
 
 import numpy as np
@@ -16,6 +22,27 @@ import torch
 
 from ..models.model import create_model, load_model
 from ..utils.image import get_affine_transform, warp_affine_normalize
+
+
+def read_image_bgr(path):
+    """An image file as cv2.imread gives it: 8-bit BGR [H, W, 3] (datasets/dataset/polygons.py reads the same way)."""
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, ::-1])
+
+
+def load_image(path):
+    """What run() makes of a path: a .npy file is the array itself, anything else an image file."""
+    return np.load(path) if path.lower().endswith(".npy") else read_image_bgr(path)
+
+
+def class_names(opt):
+    """The names the labels show: the data set's class_name without the background entry (the Cityscapes names for
+    a set that has none, c<k> beyond them)."""
+    from ..datasets.dataset.polygons import PolygonDataset
+    from ..datasets.dataset_factory import dataset_factory
+    names = getattr(dataset_factory.get(getattr(opt, "dataset", None)), "class_name", PolygonDataset.class_name)[1:]
+    return [names[k] if k < len(names) else "c%d" % k for k in range(opt.num_classes)]
 
 
 def _resize_bilinear_u8(img_dev, new_w, new_h):
@@ -28,6 +55,9 @@ def _resize_bilinear_u8(img_dev, new_w, new_h):
 
 class BaseDetector(object):
     def __init__(self, opt):
+        if getattr(opt, "debug", 0) == 3:
+            raise ValueError("--debug 3 shows the pictures with matplotlib, which is not available here: use --debug 1, "
+                             "2 or 4 (PNG files in the experiment's debug directory)")
         if opt.gpus[0] < 0:
             raise RuntimeError("centerpoly_amd detectors run on a HIP device only (--gpus -1 "
                                "has no CPU fallback)")
@@ -47,6 +77,7 @@ class BaseDetector(object):
         self.scales = opt.test_scales
         self.opt = opt
         self.pause = True
+        self.debugger = None                                 # made at the first run() with --debug >= 1, then kept
 
     def pre_process(self, image, scale, meta=None):
         height, width = image.shape[0:2]
@@ -88,14 +119,42 @@ class BaseDetector(object):
     def merge_outputs(self, detections):
         raise NotImplementedError
 
+    def debug(self, debugger, images, dets, output, scale=1):
+        raise NotImplementedError
+
+    def show_results(self, debugger, image, results):
+        raise NotImplementedError
+
     def run(self, image_or_path_or_tensor, id=1, meta=None):
+        """The same image gives the same detections, bit for bit, with and without --debug: for the duration of the
+        call the vendor library is asked for its reproducible convolution algorithms (the previous setting is put
+        back).  Only convolutions too small for the MFMA kernel reach it (hourglass: 512 -> 384 at 4 x 8); its
+        default choice there sums in an order that changes from launch to launch.  DLA-34 has none."""
+        before = torch.backends.cudnn.deterministic
+        torch.backends.cudnn.deterministic = True
+        try:
+            return self._run(image_or_path_or_tensor, id, meta)
+        finally:
+            torch.backends.cudnn.deterministic = before
+
+    def _run(self, image_or_path_or_tensor, id=1, meta=None):
         load_time = pre_time = net_time = dec_time = post_time = merge_time = 0
         start_time = time.time()
         pre_processed = False
+        debug_level = getattr(self.opt, "debug", 0)
+        debugger, stem = None, "img%s" % id
+        if debug_level >= 1:
+            if self.debugger is None:
+                from ..utils.debugger import Debugger
+                self.debugger = Debugger(class_names(self.opt), theme=getattr(self.opt, "debugger_theme", "white"),
+                                         down_ratio=self.opt.down_ratio, device=self.opt.device)
+            debugger = self.debugger
+            debugger.imgs = {}
         if isinstance(image_or_path_or_tensor, np.ndarray):
             image = image_or_path_or_tensor
         elif isinstance(image_or_path_or_tensor, str):
-            image = np.load(image_or_path_or_tensor)
+            image = load_image(image_or_path_or_tensor)
+            stem = os.path.splitext(os.path.basename(image_or_path_or_tensor))[0]
         else:
             image = image_or_path_or_tensor["image"][0].numpy()
             pre_processed_images = image_or_path_or_tensor
@@ -121,6 +180,8 @@ class BaseDetector(object):
             net_time += forward_time - pre_process_time
             decode_time = time.time()
             dec_time += decode_time - forward_time
+            if debug_level >= 2:
+                self.debug(debugger, images, dets, output, scale)
             dets = self.post_process(dets, meta, scale)
             post_process_time = time.time()
             post_time += post_process_time - decode_time
@@ -129,6 +190,13 @@ class BaseDetector(object):
         results = self.merge_outputs(detections)
         end_time = time.time()
         merge_time += end_time - post_process_time
-        return {"results": results, "tot": end_time - start_time, "load": load_time,
-                "pre": pre_time, "net": net_time, "dec": dec_time, "post": post_time,
-                "merge": merge_time}
+        ret = {"results": results, "tot": end_time - start_time, "load": load_time,
+               "pre": pre_time, "net": net_time, "dec": dec_time, "post": post_time,
+               "merge": merge_time}
+        if debug_level >= 1:
+            vis_id = self.show_results(debugger, image, results)
+            torch.cuda.synchronize()
+            ret["vis"] = debugger.imgs[vis_id]               # the overlay, still on the device
+            ret["vis_files"] = debugger.show_all_imgs(pause=self.pause, path=self.opt.debug_dir, prefix=stem + "_")
+            ret["vis_time"] = time.time() - end_time
+        return ret

@@ -38,9 +38,11 @@ class PolydetDetector(BaseDetector):
     def post_process(self, dets, meta, scale=1, fg=None):
         # transform_preds + `/ scale` on the device, one copy back, class split on the host
         dets = dets.detach().reshape(1, -1, dets.shape[2])
-        ret, rows = polydet_post_process_device(dets, [meta["c"]], [meta["s"]], meta["out_height"],
-                                                meta["out_width"], self.opt.num_classes, scale, return_device=True)
+        ret, rows, host = polydet_post_process_device(dets, [meta["c"]], [meta["s"]], meta["out_height"],
+                                                      meta["out_width"], self.opt.num_classes, scale,
+                                                      return_device=True, return_host=True)
         self.rows_dev = rows[0]                      # the same rows, still on the device (see device_rows)
+        self.rows_host = host[0]                     # ... and as they were copied back, class column included
         return ret[0]
 
     def device_rows(self, results=None):
@@ -52,6 +54,34 @@ class PolydetDetector(BaseDetector):
         rows = [np.concatenate([r[:, :5], np.full((len(r), 1), j - 1, np.float32), r[:, 5:]], axis=1)
                 for j, r in sorted(results.items())]
         return torch.from_numpy(np.ascontiguousarray(np.concatenate(rows, axis=0), np.float32)).to(self.opt.device)
+
+    def host_rows(self, results=None):
+        """The rows of device_rows on the host, row for row (the labels of the overlay are made from them)."""
+        if len(self.scales) == 1 and not self.opt.nms:
+            return self.rows_host
+        rows = [np.concatenate([r[:, :5], np.full((len(r), 1), j - 1, np.float32), r[:, 5:]], axis=1)
+                for j, r in sorted(results.items())]
+        return np.ascontiguousarray(np.concatenate(rows, axis=0), np.float32)
+
+    def debug(self, debugger, images, dets, output, scale=1):
+        """pred_hm_<scale>: the class heat maps over the network input; out_pred_<scale>: the network input with
+        the boxes of the centres above --center_thresh, in network-input coordinates (reference :78-91)."""
+        hm_id, out_id = "pred_hm_{:.1f}".format(scale), "out_pred_{:.1f}".format(scale)
+        mean, std = self.mean.reshape(3), self.std.reshape(3)
+        debugger.add_blend_img(images[0], output["hm"][0], mean, std, img_id=hm_id)
+        debugger.add_blend_img(images[0], None, mean, std, img_id=out_id)       # the de-normalised input alone
+        rows = dets[0].detach().clone()
+        rows[:, :4] *= self.opt.down_ratio
+        debugger.add_polydet_detections(rows, rows.cpu().numpy(), self.opt.center_thresh, img_id=out_id,
+                                        boxes_only=True)
+
+    def show_results(self, debugger, image, results):
+        """The picture `polydet`: box, polygon and label of every detection above --vis_thresh, drawn on the
+        device from the rows post_process left there (reference :93-100).  Returns the picture's id."""
+        debugger.add_img(image, img_id="polydet")
+        debugger.add_polydet_detections(self.device_rows(results), self.host_rows(results), self.opt.vis_thresh,
+                                        img_id="polydet")
+        return "polydet"
 
     def merge_outputs(self, detections):
         results = {}

@@ -33,7 +33,15 @@ class opts(object):
                        help="cityscapes | kitti_poly | IDD (annotation JSON + images) | synthetic (offline)")
         p.add_argument("--exp_id", default="default")
         p.add_argument("--test", action="store_true")
-        p.add_argument("--debug", type=int, default=0)
+        p.add_argument("--debug", type=int, default=0,
+                       help="detector pictures, rendered on the GPU and written as PNG files into the experiment's "
+                            "debug directory: 1 the detections, 2 also the heat-map view and the centre boxes, 4 the "
+                            "same (all files); 3 (matplotlib) is refused")
+        p.add_argument("--demo", default="", help="demo.py: an image file or a directory of images")
+        p.add_argument("--vis_thresh", type=float, default=0.3, help="detections drawn: score above it")
+        p.add_argument("--debugger_theme", default="white", choices=["white", "black"])
+        p.add_argument("--center_thresh", type=float, default=0.1,
+                       help="--debug 2: centres whose boxes the out_pred view shows")
         p.add_argument("--load_model", default="")
         p.add_argument("--resume", action="store_true")
         p.add_argument("--gpus", default="0", help="-1 is rejected: no CPU path")

@@ -49,12 +49,13 @@ def _inverse_transforms(c, s, h, w, device):
     return t
 
 
-def polydet_post_process_device(dets, c, s, h, w, num_classes, scale=1.0, return_device=False):
+def polydet_post_process_device(dets, c, s, h, w, num_classes, scale=1.0, return_device=False, return_host=False):
     """polydet_post_process + the `/ scale` of PolydetDetector.post_process with the affine of
     every box corner and vertex done on the device (cp_polydet_post_process); one device -> host
     copy of the [B,K,2N+7] rows, then the per-class split.  dets: HIP tensor [B,K,2N+7].
     Returns [{1..C: float32 [n, 2N+6]}] per image (rows x1,y1,x2,y2,score,poly(2N),depth); with return_device
-    also the device rows [B,K,2N+7] the copy was made from (class column included), for consumers on the device."""
+    also the device rows [B,K,2N+7] the copy was made from (class column included), for consumers on the device; with
+    return_host, last, the host copy of those rows as it came back."""
     import torch
 
     from .. import _C
@@ -71,4 +72,5 @@ def polydet_post_process_device(dets, c, s, h, w, num_classes, scale=1.0, return
         cls = d[:, 5]
         keep = np.concatenate([d[:, :5], d[:, 6:]], axis=1)
         ret.append({j + 1: keep[cls == j] for j in range(num_classes)})
-    return (ret, out) if return_device else ret
+    res = (ret,) + ((out,) if return_device else ()) + ((rows,) if return_host else ())
+    return res if len(res) > 1 else ret

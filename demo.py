@@ -1,0 +1,56 @@
+#!/usr/bin/env python3
+"""Demo driver with the reference's CLI (src/demo.py): `python demo.py polydet --demo <image or directory>
+--load_model model_last.pth`.  Every image (jpg, jpeg, png, webp; a directory's in sorted order) goes through the
+detector with --debug >= 1: the detections are drawn on the GPU and written as `<stem>_polydet.png` into the
+experiment's debug directory (--debug 2 adds the heat-map view and the centre boxes).  One timing line per image, as
+the reference prints it, with the time of the pictures appended.  `--load_model ''` runs the random initialisation.
+There is no video decoder here: `webcam` and video files are refused."""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+image_ext = ["jpg", "jpeg", "png", "webp"]
+video_ext = ["mp4", "mov", "avi", "mkv"]
+time_stats = ["tot", "load", "pre", "net", "dec", "post", "merge"]
+
+
+def _ext(name):
+    return name[name.rfind(".") + 1:].lower()
+
+
+def image_names(demo):
+    """The files --demo names: the images of a directory in sorted order, or the one file."""
+    if demo == "webcam" or _ext(demo) in video_ext:
+        raise ValueError("--demo %s: no video decoder is available (cv2 is absent); pass an image file or a "
+                         "directory of images" % demo)
+    if not demo:
+        raise ValueError("--demo needs an image file or a directory of images")
+    if os.path.isdir(demo):
+        return [os.path.join(demo, f) for f in sorted(os.listdir(demo)) if _ext(f) in image_ext]
+    return [demo]
+
+
+def demo(opt):
+    """Runs the detector over opt.demo; returns [(image name, run()'s dict)]."""
+    from centerpoly_amd.datasets.dataset_factory import dataset_factory
+    from centerpoly_amd.detectors.detector_factory import detector_factory
+    from centerpoly_amd.opts import opts
+    names = image_names(opt.demo)                            # refusals come before the model is built
+    os.environ["CUDA_VISIBLE_DEVICES"] = opt.gpus_str
+    opt.debug = max(opt.debug, 1)
+    opt = opts().update_dataset_info_and_set_heads(opt, dataset_factory[opt.dataset])
+    detector = detector_factory[opt.task](opt)
+    out = []
+    for name in names:
+        ret = detector.run(name)
+        print("".join("{} {:.3f}s |".format(stat, ret[stat]) for stat in time_stats)
+              + "vis {:.3f}s |".format(ret["vis_time"]))
+        out.append((name, ret))
+    return out
+
+
+if __name__ == "__main__":
+    from centerpoly_amd.opts import opts
+    demo(opts().parse())

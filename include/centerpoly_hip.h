@@ -51,7 +51,8 @@ extern "C" {
 #define CP_ABI_VERSION 3   /* 3 (round 4): + cp_polydet_decode_ex, cp_dense_l1_*, cp_polydet_dense_targets, cp_conv_direct_forward_ex,
                               cp_conv_mfma_forward_split, cp_activation_split / _unsplit, cp_dla_base_pair_*; no signature changed.
                               Added since, backward compatible (no version change): cp_polydet_targets_ex,
-                              cp_class_instance_masks, cp_class_writer_instances */
+                              cp_class_instance_masks, cp_class_writer_instances, cp_render_overlay_workspace_bytes,
+                              cp_render_overlay, cp_render_heatmap */
 
 enum {
   CP_OK = 0,
@@ -475,6 +476,60 @@ int cp_class_writer_instances(const float* rows, int32_t R, int32_t N, float thr
                               const int32_t* class_label, int32_t C, int32_t* n_out, int32_t* src, int32_t* poly,
                               int32_t* group, uint8_t* flags, int32_t* label, float* conf, int32_t* text_index,
                               void* stream);
+
+/* ------------------------------------------------ detection overlays (demo.py, --debug) --
+ * cp_render_overlay: the picture of ONE image's detections, composed on the device from the instance list
+ * cp_writer_instances left there (run with thresh = vis_thresh and a class table in which every class has masks).
+ *   image  DEVICE uint8 [H][W][3], the channel order is the caller's          out  DEVICE uint8 [H][W][3], may be image
+ *   rows   DEVICE fp32 [R][2N + 7], the rows the list was made from           n    DEVICE int32 [1], cp_writer_instances' n_out
+ *   src    DEVICE int32 [R]      poly  DEVICE int32 [R][N][2]                 palette  DEVICE uint8 [C][3]
+ *   label_codes  DEVICE int32 [R][L]: per SOURCE row the glyph codes of its label, ended by a negative code
+ *   atlas  DEVICE uint8 [G][11][6]: non-zero = set pixel of glyph g in its 6 x 11 cell (a code >= G is a blank cell)
+ * The list is nearest first; instance i has paint index p = n - 1 - i (farthest painted first) and contributes, in
+ * this order, with (x1, y1, x2, y2) the row's box truncated toward zero to int32 and colour = palette[class]
+ * (255 - palette[class] under white_theme):
+ *   1 fill      the pixels ImageDraw.polygon(pts, fill=...) of PIL 12.2 sets: (orig * (256 - alpha) + colour * alpha
+ *               + 128) >> 8 per channel, orig being the INPUT image;
+ *   2 outline   the pixels ImageDraw.polygon(pts, outline=...) sets, dilated by the (2 r + 1)^2 square, clipped:
+ *               outline_colour;
+ *   3 box       the pixels x1 <= x <= x2, y1 <= y <= y2 with min(x - x1, x2 - x, y - y1, y2 - y) < box_thickness: colour;
+ *   4 label background   x1 <= x < x1 + 6 len, y1 - 12 <= y <= y1 - 2 (len = the label's length): colour;
+ *   5 label glyphs       the set pixels of glyph j in the cell at (x1 + 6 j, y1 - 12): (0, 0, 0).
+ * A pixel shows the last operation covering it in the order (p, operation); untouched pixels keep the input.  show_txt
+ * == 0 (or L == 0) drops 4 and 5 (label_codes and atlas may then be null), show_polygons == 0 drops 1 and 2.  An
+ * instance whose polygon has a coordinate beyond +-2^29 contributes 3, 4 and 5 only (no defined drawing that far out).  With n > 128 nothing is drawn (out =
+ * image): n is on the device, the caller refuses it when it reads n.  Integer arithmetic, the same bits on every run.
+ * R <= 1024, 3 <= N <= 64, C <= 32, L <= 16, G <= 128, H * W < 2^31, outline_radius <= 16: beyond, CP_EUNSUPPORTED;
+ * null pointers, alpha outside 0..256, a negative radius or thickness: CP_EINVAL; workspace shorter than
+ * cp_render_overlay_workspace_bytes (the per-pixel operation map, 4 bytes a pixel): CP_EWORKSPACE.  All checks come
+ * before any device work.  One memset and two launches whatever n is.
+ *
+ * cp_render_heatmap: the reference's gen_colormap + add_blend_img (utils/debugger.py) in one launch:
+ *   cm[k] = max over c of uint8(hm[c][y / ratio][x / ratio] * palette[c % P][k]) (an fp32 product, truncated),
+ *   255 - cm under `white`; back[k] = uint8((input[k][y][x] * std[k] + mean[k]) * 255), every step rounded to fp32,
+ *   kept in 0..255; out[y][x][k] = (back * 77 + cm * 179 + 128) >> 8.
+ *   hm  DEVICE fp32 [C][h][w], activated      input  DEVICE fp32 [3][h * ratio][w * ratio]      mean, std  HOST fp32 [3]
+ *   palette  DEVICE uint8 [P][3], P <= 32     out    DEVICE uint8 [h * ratio][w * ratio][3]
+ * C == 0 (hm may be null) writes out = back, the de-normalised network input alone. */
+typedef struct cp_overlay_params {
+  int32_t alpha;              /* 0 .. 256, weight of the class colour in the fill */
+  int32_t outline_radius;     /* r */
+  int32_t box_thickness;      /* t */
+  int32_t white_theme;
+  int32_t show_txt;           /* 0 drops operations 4 and 5 */
+  int32_t show_polygons;      /* 0 drops operations 1 and 2 (boxes and labels alone) */
+  uint8_t outline_colour[3];  /* in the image's channel order */
+  uint8_t reserved;
+} cp_overlay_params;
+size_t cp_render_overlay_workspace_bytes(int32_t H, int32_t W);
+int cp_render_overlay(const uint8_t* image, int32_t H, int32_t W, const float* rows, int32_t R, int32_t N,
+                      const int32_t* n, const int32_t* src, const int32_t* poly, const uint8_t* palette, int32_t C,
+                      const int32_t* label_codes, int32_t L, const uint8_t* atlas, int32_t G,
+                      const cp_overlay_params* params, uint8_t* out, void* workspace, size_t workspace_bytes,
+                      void* stream);
+int cp_render_heatmap(const float* hm, int32_t C, int32_t h, int32_t w, int32_t ratio, const float* input,
+                      const float* mean, const float* stdv, const uint8_t* palette, int32_t P, int32_t white,
+                      uint8_t* out, void* stream);
 
 /* ------------------------------------------------ detector pre/post-processing --
  * cp_preprocess_warp_normalize: the cv2 stage of BaseDetector.pre_process
