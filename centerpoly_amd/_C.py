@@ -86,6 +86,7 @@ _SIGNATURES = {
     "cp_render_overlay": (c_int32, [_P, c_int32, c_int32, _P, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, c_int32, _P,
                                     c_int32, _P, _P, _P, c_size_t, _P]),
     "cp_render_heatmap": (c_int32, [_P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, c_int32, c_int32, _P, _P]),
+    "cp_oracle_map": (c_int32, [_P, _P] + [c_int32] * 5 + [_P, _P]),
     "cp_id_histogram": (c_int32, [_P, c_int32, c_int32, _P, _P]),
     "cp_instance_overlaps_workspace_bytes": (c_size_t, [c_int32] * 4),
     "cp_instance_overlaps": (c_int32, [_P, c_int32, _P, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P,

@@ -131,9 +131,19 @@ class opts(object):
         p.add_argument("--elliptical_gt", action="store_true",
                        help="elliptical centre heat maps, stretched along the longer box side "
                             "(draw_ellipse_gaussian); needs device-built targets")
-        for flag in ("eval_oracle_hm", "eval_oracle_border_hm", "eval_oracle_offset",
-                     "eval_oracle_poly", "eval_oracle_pseudo_depth"):
-            p.add_argument("--" + flag, action="store_true")
+        # ground truth in place of a head's output, for --test / validation: the AP a perfect head would give (the
+        # replaced head gets no gradient)
+        for flag, what in (
+                ("eval_oracle_hm", "use the ground-truth centre heat map instead of the hm head (hm_l and loss are "
+                                   "then NaN for every image with an object, as in the reference)"),
+                ("eval_oracle_border_hm", "put the ground-truth border heat map into the outputs (nothing reads it); "
+                                          "device-built targets then carry border_hm"),
+                ("eval_oracle_offset", "use the ground-truth centre offsets instead of the reg head"),
+                ("eval_oracle_poly", "use the ground-truth polygons instead of the poly head (not with "
+                                     "--cat_spec_poly)"),
+                ("eval_oracle_pseudo_depth", "use the ground-truth depth order instead of the pseudo_depth head")):
+            p.add_argument("--" + flag, action="store_true",
+                           help=what + "; for --test / validation, an upper bound of the score, not for training")
         self.parser = p
 
     def parse(self, args=""):

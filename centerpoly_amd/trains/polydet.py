@@ -4,27 +4,37 @@ Aggregation, weights, returned stats keys and the in-place activation of
 output['hm'] follow the reference; every term is a HIP kernel and stays a device
 scalar.  `--dense_poly` (:107-110) is a dense masked-L1 kernel; `--cat_spec_poly` (:103-106) hands PolyLoss a
 [B, M, C*2N] mask whose rows `if mask[batch][i]:` cannot reduce to a bool -- the reference raises RuntimeError on the first
-object (models/losses.py:870) and so does this mirror.  The `--eval_oracle_*` switches (:49-70, numba BFS maps of an
-evaluation-protocol experiment, all default off) raise NotImplementedError.
+object (models/losses.py:870) and so does this mirror.
+
+The `--eval_oracle_*` switches (:49-70, all default off) replace entries of the `output` dict by the ground truth after
+the activation and before the criteria, so ModelWithLoss returns them and save_result decodes them: the AP of a run
+with a perfect heat map / offset / polygon / depth head.  hm and border_hm take the batch's tensors themselves; reg, poly
+and pseudo_depth become dense maps through utils.oracle_utils.gen_oracle_map, one HIP launch each where the reference
+floods the map on the host.  The replaced heads carry no gradient, as there: the switches are for --test / validation.
+With the heat map replaced the focal term is the reference's _neg_loss on (gt, gt), log(1 - 1) * 1 * 0 * 0 at every
+positive: hm_l and loss are NaN whenever an image has an object, and this mirror returns that NaN.
 """
 import torch
 
 from ..models.decode import polydet_decode
 from ..models.losses import (FocalLoss, MSELoss, PolyLoss, RegL1Loss, RegLoss, dense_poly_l1_loss,
                              sigmoid_focal_loss)
+from ..utils.oracle_utils import gen_oracle_map
 from ..utils.post_process import polydet_post_process
 from .base_trainer import BaseTrainer
 
-_UNSUPPORTED = ("eval_oracle_hm", "eval_oracle_border_hm", "eval_oracle_offset",
-                "eval_oracle_poly", "eval_oracle_pseudo_depth")
+# --eval_oracle_<flag> -> the head (and batch key) whose map gen_oracle_map rebuilds from the per-object targets
+_ORACLE_MAPS = (("eval_oracle_offset", "reg"), ("eval_oracle_poly", "poly"),
+                ("eval_oracle_pseudo_depth", "pseudo_depth"))
 
 
 class PolydetLoss(torch.nn.Module):
     def __init__(self, opt):
         super(PolydetLoss, self).__init__()
-        for flag in _UNSUPPORTED:
-            if getattr(opt, flag, False):
-                raise NotImplementedError("--%s is outside the accelerated polydet path" % flag)
+        if getattr(opt, "eval_oracle_poly", False) and getattr(opt, "cat_spec_poly", False):
+            # the reference hands the 2N-channel map of batch['poly'] to a decode that reads C * 2N channels
+            raise ValueError("--eval_oracle_poly cannot be combined with --cat_spec_poly: the oracle polygon map has "
+                             "2N channels, the class-specific decode expects C * 2N")
         if getattr(opt, "reg_loss", "l1") not in ("l1", "sl1"):
             raise NotImplementedError("--reg_loss must be l1 or sl1 (the reference leaves crit_reg None otherwise)")
         self.mse = bool(getattr(opt, "mse_loss", False))
@@ -38,11 +48,20 @@ class PolydetLoss(torch.nn.Module):
         hm_loss = off_loss = poly_loss = depth_loss = order_loss = 0
         for s in range(opt.num_stacks):
             output = outputs[s]
+            oracle_hm = getattr(opt, "eval_oracle_hm", False)
+            if oracle_hm:                    # :49-50, the tensor itself; the activated head is dropped unread
+                output["hm"] = batch["hm"]
+            if getattr(opt, "eval_oracle_border_hm", False):         # :53-54, a key nothing reads
+                output["border_hm"] = batch["border_hm"]
+            for flag, head in _ORACLE_MAPS:                          # :55-70
+                if getattr(opt, flag, False):
+                    output[head] = gen_oracle_map(batch[head], batch["ind"], output[head].shape[3],
+                                                  output[head].shape[2])
             depth_loss = depth_loss + self.crit_reg(
                 output["pseudo_depth"], batch["reg_mask"], batch["ind"],
                 batch["pseudo_depth"]) / opt.num_stacks
-            if self.mse:                     # --mse_loss: MSE on the raw head, no activation (:44-46,84)
-                hm_l = self.crit(output["hm"], batch["hm"])
+            if self.mse or oracle_hm:        # --mse_loss: MSE on the raw head, no activation (:44-46,84);
+                hm_l = self.crit(output["hm"], batch["hm"])          # --eval_oracle_hm: the criterion on (gt, gt)
             else:                            # _sigmoid + FocalLoss fused; output['hm'] becomes the activated map
                 hm_l, output["hm"] = sigmoid_focal_loss(output["hm"], batch["hm"])
             hm_loss = hm_loss + hm_l / opt.num_stacks
@@ -115,7 +134,8 @@ class PolydetTrainer(BaseTrainer):
         h, w = batch["input"].shape[2] // opt.down_ratio, batch["input"].shape[3] // opt.down_ratio
         targets = build_targets(batch, h, w, opt.num_classes, rep=opt.rep,
                                 no_reorder_flip=getattr(opt, "no_reorder_flip", False),
-                                with_border_hm=False, dense_poly=getattr(opt, "dense_poly", False),
+                                with_border_hm=getattr(opt, "eval_oracle_border_hm", False),
+                                dense_poly=getattr(opt, "dense_poly", False),
                                 cat_spec_poly=getattr(opt, "cat_spec_poly", False),
                                 elliptical_gt=getattr(opt, "elliptical_gt", False))
         out = {k: v for k, v in batch.items() if k in ("input", "meta")}

@@ -531,6 +531,25 @@ int cp_render_heatmap(const float* hm, int32_t C, int32_t h, int32_t w, int32_t 
                       const float* mean, const float* stdv, const uint8_t* palette, int32_t P, int32_t white,
                       uint8_t* out, void* stream);
 
+/* ------------------------------------------------ ground-truth head maps (--eval_oracle_*) --
+ * cp_oracle_map: the reference's gen_oracle_map (src/lib/utils/oracle_utils.py), a 4-neighbour breadth-first flood
+ * fill from the objects' centres over the whole map, in its closed form and in one launch:
+ *   feat  DEVICE fp32 [B][M][D]       ind  DEVICE int64 [B][M], flat index y * w + x of object j's centre
+ *   out   DEVICE fp32 [B][D][h][w], every element written (no need to clear it)
+ * Per image, object j is a seed when ind[j] > 0 -- not reg_mask: padding rows are skipped, and so is a real object
+ * whose centre is flat index 0, as in the reference.  Then
+ *   out[b][:][y][x] = feat[b][j*][:], j* = the LOWEST j among the seeds at minimal |x - x_j| + |y - y_j|
+ * (the BFS level of a pixel is its L1 distance to the nearest seed, and the queue keeps each level in seed order),
+ * with one exception: at a seed's own pixel the HIGHEST j with that ind wins (later duplicates overwrite the pixel,
+ * the earlier one expands first).  An image without a seed is all zeros.  The values are copies: bit-exact.
+ * ind[j] >= h * w: the reference indexes out of bounds there and defines nothing; here such an object is skipped like
+ * ind <= 0.  This is the one place where the reference leaves the result open.
+ * M <= 1024, B <= 65535, h * w < 2^31 (CP_EUNSUPPORTED beyond); any D (a loop over channels), any h and w, any
+ * alignment (16-byte stores where w % 4 == 0 and out is 16-byte aligned).  Null pointers or non-positive sizes:
+ * CP_EINVAL.  All checks come before any device work. */
+int cp_oracle_map(const float* feat, const int64_t* ind, int32_t B, int32_t M, int32_t D, int32_t h, int32_t w,
+                  float* out, void* stream);
+
 /* ------------------------------------------------ detector pre/post-processing --
  * cp_preprocess_warp_normalize: the cv2 stage of BaseDetector.pre_process
  * (src/lib/detectors/base_detector.py:66-87): cv2.warpAffine(image, trans_input, (dst_w, dst_h),
