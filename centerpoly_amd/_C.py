@@ -82,6 +82,13 @@ _SIGNATURES = {
     "cp_writer_instances": (c_int32, [_P, c_int32, c_int32, c_float, _P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "cp_class_instance_masks": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
     "cp_class_writer_instances": (c_int32, [_P, c_int32, c_int32, c_float, c_int32, _P, c_int32] + [_P] * 9),
+    "cp_annot_id_instances_workspace_bytes": (c_size_t, []),
+    "cp_annot_id_instances": (c_int32, [_P, c_int32, c_int32, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
+                                        c_size_t, _P]),
+    "cp_polygon_masks_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "cp_polygon_masks": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
+    "cp_annot_rays_ids": (c_int32, [_P, c_int32, c_int32, _P, _P, c_int32, c_int32, _P, _P]),
+    "cp_annot_rays_masks": (c_int32, [_P, c_int32, c_int32, _P, c_int32, c_int32, _P, _P]),
     "cp_render_overlay_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "cp_render_overlay": (c_int32, [_P, c_int32, c_int32, _P, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, c_int32, _P,
                                     c_int32, _P, _P, _P, c_size_t, _P]),

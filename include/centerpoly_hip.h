@@ -477,6 +477,57 @@ int cp_class_writer_instances(const float* rows, int32_t R, int32_t N, float thr
                               int32_t* group, uint8_t* flags, int32_t* label, float* conf, int32_t* text_index,
                               void* stream);
 
+/* ------------------------------------------------ training annotations (make_annotations.py) --
+ * The "regular interval" recipe of the reference's offline annotation tools (KITTIPolyStuff/Tools/
+ * create_annotations.py:107-166, cityscapesStuff/Tools/create_bouding_box_annotations.py:135-215, IDDStuff/Tools/
+ * create_annotations.py:100-166) for the objects of ONE image.  With k = N / 4, qx = (x1 - x0) / k and qy = (y1 - y0) / k
+ * in fp64, vertex j of an object with box (x0, y0, x1, y1) starts at
+ *   j = i:       (round(x0 + i qx), y0)      j = k + i:   (x1, round(y0 + i qy))
+ *   j = 2k + i:  (round(x1 - i qx), y1)      j = 3k + i:  (x0, round(y1 - i qy))          i = 0 .. k-1
+ * (round = half-to-even on the fp64 value fl(x0 + fl(i q)), no FMA; both coordinates then truncated towards zero),
+ * walks the `bresenham` package's line to the centre (int(x0 + (x1 - x0) / 2), int(y0 + (y1 - y0) / 2)), both ends
+ * included, every pixel clipped to the canvas, and is the first clipped pixel whose mask is set -- the clipped centre
+ * when there is none.  Integer results, the same bits on every run.  All checks come before any device work.
+ *
+ * cp_annot_id_instances: the objects of a 16-bit instance image v = label * divisor + k (the KITTI tool: divisor 256).
+ *   ids   DEVICE uint16 [H][W]        class_label  HOST int32 [C]: label of class 0 .. C-1
+ *   n_out DEVICE int32 [1]: the distinct non-zero values whose v / divisor is one of class_label
+ *   inst_id DEVICE int32 [max_inst]: those values, ascending (the place in this order is the tool's pseudo-depth)
+ *   cls   DEVICE int32 [max_inst]: the class       box  DEVICE int32 [max_inst][4]: min x, min y, max x, max y of its pixels
+ * Slots at n_out and above: inst_id 0, cls -1, box 0.  More than max_inst objects are reported through n_out; the
+ * caller refuses them.  1 <= C <= 32, 1 <= max_inst <= 1024, H * W < 2^31 (CP_EUNSUPPORTED beyond); any H, W and
+ * alignment.  workspace: cp_annot_id_instances_workspace_bytes (the box table of 65536 values); shorter: CP_EWORKSPACE.
+ *
+ * cp_polygon_masks: ImageDraw.polygon(pts, outline=0, fill=255) on a fresh 'L' image for each of n polygons on its
+ * own canvas -- F \ O in the words of cp_class_instance_masks, no occlusion -- for polygons of any length.
+ *   xy     DEVICE int32 [T][2]: the vertices of all polygons, one after the other
+ *   first  HOST int32 [n + 1]: polygon i is xy[first[i] .. first[i + 1]), first[0] = 0, T = first[n]
+ *   masks  DEVICE uint8 [n][H][W] out, 0 / 255, any alignment      counts DEVICE int32 [n] out, non-zero pixels
+ * n <= 128, 3 <= vertices of a polygon <= 4096, H * W < 2^31 (CP_EUNSUPPORTED beyond; fewer than 3 vertices or a
+ * first[] that does not start at 0: CP_EINVAL).  The arithmetic is csrc/class_masks_core.h, exact for vertices within
+ * +-2^24.  workspace: cp_polygon_masks_workspace_bytes(n, T) (the edge table); shorter: CP_EWORKSPACE.  A fixed number
+ * of launches whatever n and T.
+ *
+ * cp_annot_rays_ids / cp_annot_rays_masks: the N vertices of n objects; the mask of object i is ids == inst_id[i],
+ * or masks[i] > 0.
+ *   box   DEVICE fp64 [n][4]: x0, y0, x1, y1 as the tool holds them (integers for an id image, the untruncated
+ *         numbers of a polygon file)            inst_id DEVICE int32 [n]
+ *   poly  DEVICE int32 [n][N][2] out
+ * 4 <= N <= 64 and N % 4 == 0 (otherwise CP_EINVAL, beyond 64 CP_EUNSUPPORTED), n <= 1024, H * W < 2^31.  Every mask
+ * read is clipped to the canvas and every walk ends with its line, whatever the box holds (coordinates are kept
+ * within +-2^29, a NaN at 0; the recipe is the tools' for boxes within +-2^24). */
+size_t cp_annot_id_instances_workspace_bytes(void);
+int cp_annot_id_instances(const uint16_t* ids, int32_t H, int32_t W, const int32_t* class_label, int32_t C,
+                          int32_t divisor, int32_t max_inst, int32_t* n_out, int32_t* inst_id, int32_t* cls,
+                          int32_t* box, void* workspace, size_t workspace_bytes, void* stream);
+size_t cp_polygon_masks_workspace_bytes(int32_t n, int32_t total_vertices);
+int cp_polygon_masks(const int32_t* xy, const int32_t* first, int32_t n, int32_t H, int32_t W, uint8_t* masks,
+                     int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int cp_annot_rays_ids(const uint16_t* ids, int32_t H, int32_t W, const int32_t* inst_id, const double* box, int32_t n,
+                      int32_t N, int32_t* poly, void* stream);
+int cp_annot_rays_masks(const uint8_t* masks, int32_t H, int32_t W, const double* box, int32_t n, int32_t N,
+                        int32_t* poly, void* stream);
+
 /* ------------------------------------------------ detection overlays (demo.py, --debug) --
  * cp_render_overlay: the picture of ONE image's detections, composed on the device from the instance list
  * cp_writer_instances left there (run with thresh = vis_thresh and a class table in which every class has masks).
