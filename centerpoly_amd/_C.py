@@ -89,6 +89,8 @@ _SIGNATURES = {
     "cp_polygon_masks": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
     "cp_annot_rays_ids": (c_int32, [_P, c_int32, c_int32, _P, _P, c_int32, c_int32, _P, _P]),
     "cp_annot_rays_masks": (c_int32, [_P, c_int32, c_int32, _P, c_int32, c_int32, _P, _P]),
+    "cp_polygon_paint_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "cp_polygon_paint": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_size_t, _P]),
     "cp_render_overlay_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "cp_render_overlay": (c_int32, [_P, c_int32, c_int32, _P, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, c_int32, _P,
                                     c_int32, _P, _P, _P, c_size_t, _P]),

@@ -528,6 +528,30 @@ int cp_annot_rays_ids(const uint16_t* ids, int32_t H, int32_t W, const int32_t* 
 int cp_annot_rays_masks(const uint8_t* masks, int32_t H, int32_t W, const double* box, int32_t n, int32_t N,
                         int32_t* poly, void* stream);
 
+/* ------------------------------------------------ ground-truth id images (make_ground_truth.py) --
+ * cp_polygon_paint: the painter of the evaluators' preparation scripts (IDDscripts/preperation/json2instanceImg.py:
+ * 132-206 and json2labelImg.py:85-146, cityscapesscripts/preparation/json2instanceImg.py:111-166 and json2labelImg.py:
+ * 78-122) for ONE image: a canvas of `background`, then ImageDraw.polygon(pts, fill=value[i]) for i = 0 .. n-1 in this
+ * order, each overwriting what lies under it.  image[y][x] = value[i] of the LARGEST i whose fill F_i holds (x, y),
+ * `background` where there is none; F is the fill of cp_class_instance_masks (no outline), the arithmetic
+ * csrc/class_masks_core.h, exact for vertices within +-2^24.  A polygon of two vertices (a, b) is drawn as F of
+ * (a, b, a): PIL's edge list for it.
+ *   xy     DEVICE int32 [T][2]: the vertices of all polygons, one after the other
+ *   first  HOST int32 [n + 1]: polygon i is xy[first[i] .. first[i + 1]), first[0] = 0, T = first[n]; ordinary
+ *          (pageable) host memory has been read when the call returns, pinned memory only when the stream reaches
+ *          the copy: keep a pinned array unchanged until then
+ *   value  DEVICE int32 [n]           image  DEVICE int32 [H][W] out
+ * 0 <= n <= 4096 (n = 0: the background image; xy, first, value and workspace may then be null), 2 <= vertices of a
+ * polygon <= 4096, T <= 2^20, H * W < 2^31, W <= 16384 (the row is held in LDS): beyond the upper limits
+ * CP_EUNSUPPORTED; null pointers, first[0] != 0, a polygon of fewer than 2 vertices, non-positive H or W: CP_EINVAL.
+ * workspace: cp_polygon_paint_workspace_bytes(n, T) (the edge table, `first` and the y-ranges); shorter: CP_EWORKSPACE.
+ * All checks come before any device work.  Nothing is written outside the canvas, whatever the vertices hold.  One
+ * workgroup per row walks the polygons in order: no atomics on memory, no read-modify-write of the image, one copy and
+ * two launches whatever n is, the same bits on every run. */
+size_t cp_polygon_paint_workspace_bytes(int32_t n, int32_t total_vertices);
+int cp_polygon_paint(const int32_t* xy, const int32_t* first, const int32_t* value, int32_t n, int32_t background,
+                     int32_t H, int32_t W, int32_t* image, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------ detection overlays (demo.py, --debug) --
  * cp_render_overlay: the picture of ONE image's detections, composed on the device from the instance list
  * cp_writer_instances left there (run with thresh = vis_thresh and a class table in which every class has masks).
