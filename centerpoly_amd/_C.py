@@ -78,6 +78,8 @@ _SIGNATURES = {
     "cp_preprocess_warp_normalize": (c_int32, [_P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "cp_color_aug_workspace_bytes": (c_size_t, []),
     "cp_color_aug_normalize": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cp_sample_inputs_workspace_bytes": (c_size_t, [c_int32] * 3),
+    "cp_sample_inputs_batch": (c_int32, [_P] * 7 + [c_int32] * 3 + [_P, _P, c_size_t, _P]),
     "cp_instance_masks": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
     "cp_writer_instances": (c_int32, [_P, c_int32, c_int32, c_float, _P, c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "cp_class_instance_masks": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),

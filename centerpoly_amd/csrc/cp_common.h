@@ -33,6 +33,26 @@ __device__ __forceinline__ double cp_wave_sum_d(double v) {
   return v;
 }
 
+// cv::warpAffine's in-place inversion of the forward 2x3 map (float64, host): trans src -> dst, M dst -> src.
+static inline void cp_invert_affine(const double* trans, double* M) {
+  for (int i = 0; i < 6; ++i) M[i] = trans[i];
+  double D = M[0] * M[4] - M[1] * M[3];
+  D = D != 0 ? 1. / D : 0;
+  const double A11 = M[4] * D, A22 = M[0] * D;
+  M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
+  const double b1 = -M[0] * M[2] - M[1] * M[5];
+  const double b2 = -M[3] * M[2] - M[4] * M[5];
+  M[2] = b1; M[5] = b2;
+}
+
+// cvRound(v * 2^10), saturated to int: the fixed-point source coordinate of cv::warpAffine.
+__device__ __forceinline__ long long cp_round_fix(double v) {
+  const double s = v * 1024.0;
+  if (s >= 2147483647.0) return 2147483647ll;
+  if (s <= -2147483648.0) return -2147483648ll;
+  return (long long)__double2int_rn(s);                      // round half to even
+}
+
 // The result writers' vertex, int(float("%.2f" % v)), without text: two decimals round |v| up to the next integer
 // exactly when its fraction is above 0.995 (a float32 fraction is never the tie itself); the sign is kept, as int()
 // truncates towards zero.

@@ -34,22 +34,15 @@ struct PreArgs {
   int sh, sw, dh, dw, flip;
 };
 
-__device__ __forceinline__ long long round_fix(double v) {   // cvRound(v * 2^10), saturated to int
-  const double s = v * 1024.0;
-  if (s >= 2147483647.0) return 2147483647ll;
-  if (s <= -2147483648.0) return -2147483648ll;
-  return (long long)__double2int_rn(s);                      // round half to even
-}
-
 __global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) {
   const int x = blockIdx.x * 256 + threadIdx.x;
   const int y = blockIdx.y;
   if (x >= a.dw) return;
   // explicit rn ops: the compiler must not contract M1*y + M2 into an fma
-  const long long X0 = round_fix(__dadd_rn(__dmul_rn(a.m[1], (double)y), a.m[2])) + 16;
-  const long long Y0 = round_fix(__dadd_rn(__dmul_rn(a.m[4], (double)y), a.m[5])) + 16;
-  const long long X = (X0 + round_fix(__dmul_rn(a.m[0], (double)x))) >> 5;
-  const long long Y = (Y0 + round_fix(__dmul_rn(a.m[3], (double)x))) >> 5;
+  const long long X0 = cp_round_fix(__dadd_rn(__dmul_rn(a.m[1], (double)y), a.m[2])) + 16;
+  const long long Y0 = cp_round_fix(__dadd_rn(__dmul_rn(a.m[4], (double)y), a.m[5])) + 16;
+  const long long X = (X0 + cp_round_fix(__dmul_rn(a.m[0], (double)x))) >> 5;
+  const long long Y = (Y0 + cp_round_fix(__dmul_rn(a.m[3], (double)x))) >> 5;
   const int sx = (int)min(max(X >> 5, -32768ll), 32767ll);   // saturate_cast<short>
   const int sy = (int)min(max(Y >> 5, -32768ll), 32767ll);
   const int fx = (int)(X & 31), fy = (int)(Y & 31);
@@ -128,16 +121,7 @@ extern "C" int cp_preprocess_warp_normalize(const uint8_t* src, int32_t src_h, i
   PreArgs a;
   a.src = src; a.out = out;
   // cv::warpAffine inverts the forward map in place, in float64
-  double M[6];
-  for (int i = 0; i < 6; ++i) M[i] = trans[i];
-  double D = M[0] * M[4] - M[1] * M[3];
-  D = D != 0 ? 1. / D : 0;
-  const double A11 = M[4] * D, A22 = M[0] * D;
-  M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
-  const double b1 = -M[0] * M[2] - M[1] * M[5];
-  const double b2 = -M[3] * M[2] - M[4] * M[5];
-  M[2] = b1; M[5] = b2;
-  for (int i = 0; i < 6; ++i) a.m[i] = M[i];
+  cp_invert_affine(trans, a.m);
   for (int c = 0; c < 3; ++c) { a.mean[c] = (double)mean[c]; a.stdv[c] = (double)stdv[c]; }
   a.sh = src_h; a.sw = src_w; a.dh = dst_h; a.dw = dst_w; a.flip = flip_copy ? 1 : 0;
   hipLaunchKernelGGL(preprocess_kernel, dim3((dst_w + 255) / 256, dst_h), dim3(256), 0,

@@ -123,7 +123,8 @@ class PolydetDataset(torch.utils.data.Dataset):
                              (cp_preprocess_warp_normalize), colour augmentation + normalisation
                              (cp_color_aug_normalize), all training targets (cp_polydet_targets)
 
-    Items of one batch must have equal image sizes (true for Cityscapes / KITTI crops of one size)."""
+    The images of one batch may differ in size (KITTI's frames, IDD's two resolutions): the train loader collates
+    with `collate_ragged` and `build_inputs_batch` forms the dense batch on the device (cp_sample_inputs_batch)."""
 
     def _get_border(self, border, size):
         i = 1
@@ -219,4 +220,58 @@ def build_inputs(image_u8, trans_input, color, mean, std, input_h, input_w):
         _C.check(lib.cp_color_aug_normalize(_C.c_void_p(out[b].data_ptr()), int(input_h) * int(input_w),
                                             1 if col[0] != 0 else 0, P(order), P(alpha), P(light), P(m), P(sd),
                                             _C.ptr(ws), nws, _C.stream()), "cp_color_aug_normalize")
+    return out
+
+
+def collate_ragged(items):
+    """DataLoader `collate_fn` for items whose images differ in size: pops `image_u8` from every item, lays the images
+    back to back in `image_flat` (uint8, 1-D) with `image_hw` (int32 [B,2]) and `image_offset` (int64 [B], byte offset
+    of image b), and default-collates the rest (`meta` included when present).  Items without `image_u8` (the
+    synthetic set hands on a ready `input`) are default-collated as they are.  Host only, no arithmetic."""
+    from torch.utils.data import default_collate
+    if not any("image_u8" in it for it in items):
+        return default_collate(items)
+    images = [np.ascontiguousarray(it["image_u8"]) for it in items]
+    for im in images:
+        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+            raise TypeError("collate_ragged needs uint8 [H,W,3] images (got %s %s)" % (im.dtype, im.shape))
+    batch = default_collate([{k: v for k, v in it.items() if k != "image_u8"} for it in items])
+    sizes = np.array([im.size for im in images], dtype=np.int64)
+    batch["image_flat"] = torch.from_numpy(np.concatenate([im.reshape(-1) for im in images]))
+    batch["image_hw"] = torch.from_numpy(np.array([im.shape[:2] for im in images], dtype=np.int32))
+    batch["image_offset"] = torch.from_numpy(np.cumsum(sizes) - sizes)
+    return batch
+
+
+def build_inputs_batch(image_flat, image_hw, image_offset, trans_input, color, mean, std, input_h, input_w):
+    """Device half of the sampler's image path for a ragged batch (`collate_ragged`): image_flat uint8 1-D HIP tensor
+    (the B images back to back, already mirrored where flipped), image_hw [B,2] / image_offset [B] / trans_input
+    [B,6] / color [B,10] host arrays or tensors -> network input fp32 [B,3,h,w], image for image what `build_inputs`
+    gives (cp_sample_inputs_batch: two launches for the batch)."""
+    import ctypes
+    if not image_flat.is_cuda:
+        raise _C.NativeError("build_inputs_batch needs HIP device tensors; there is no CPU fallback")
+    if image_flat.dtype != torch.uint8 or image_flat.dim() != 1:
+        raise TypeError("build_inputs_batch needs a 1-D uint8 image buffer")
+    host = lambda a, dt: np.ascontiguousarray(a.cpu().numpy() if torch.is_tensor(a) else a, dtype=dt)
+    hw = host(image_hw, np.int32).reshape(-1, 2)
+    B = hw.shape[0]
+    off = host(image_offset, np.int64).reshape(B)
+    trans = host(trans_input, np.float64).reshape(B, 6)
+    col = host(color, np.float64).reshape(B, 10)
+    # the library cannot see the buffer's length: every image must lie inside it
+    if B == 0 or (hw <= 0).any() or (off < 0).any() or \
+            (off + hw[:, 0].astype(np.int64) * hw[:, 1] * 3 > image_flat.numel()).any():
+        raise ValueError("image_offset / image_hw do not describe images inside image_flat (%d bytes)"
+                         % image_flat.numel())
+    m = np.ascontiguousarray(np.asarray(mean, np.float32).ravel()[:3])
+    sd = np.ascontiguousarray(np.asarray(std, np.float32).ravel()[:3])
+    lib = _C.lib()
+    out = torch.empty((B, 3, int(input_h), int(input_w)), dtype=torch.float32, device=image_flat.device)
+    nws = lib.cp_sample_inputs_workspace_bytes(B, int(input_h), int(input_w))
+    ws = _C.workspace(nws, image_flat.device)
+    P = lambda arr: ctypes.c_void_p(arr.ctypes.data)
+    _C.check(lib.cp_sample_inputs_batch(_C.ptr(image_flat), P(off), P(hw), P(trans), P(col), P(m), P(sd), B,
+                                        int(input_h), int(input_w), _C.ptr(out), _C.ptr(ws), nws, _C.stream()),
+             "cp_sample_inputs_batch")
     return out

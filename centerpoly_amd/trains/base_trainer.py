@@ -83,7 +83,7 @@ class BaseTrainer(object):
                 break
             data_time.update(time.time() - end)
             for k in batch:
-                if k != "meta":
+                if k != "meta" and k not in self.host_keys:
                     batch[k] = batch[k].to(device=opt.device, non_blocking=True)
             batch = self.prepare_batch(batch)
             with torch.set_grad_enabled(train):
@@ -103,6 +103,8 @@ class BaseTrainer(object):
         ret = {k: v.avg for k, v in avg.items()}
         ret["time"] = (time.time() - t0) / 60.0
         return ret, results
+
+    host_keys = ()              # batch entries the host reads in prepare_batch: not uploaded
 
     def prepare_batch(self, batch):
         """Hook between the batch upload and the step (device-side target construction)."""

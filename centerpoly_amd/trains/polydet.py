@@ -105,6 +105,10 @@ class PolydetLoss(torch.nn.Module):
 
 
 class PolydetTrainer(BaseTrainer):
+    # the small per-image tables of the sampler's image path travel in kernel arguments: they stay on the host, where
+    # build_inputs / build_inputs_batch read them (uploaded, each would come back in a blocking copy every step)
+    host_keys = ("trans_input", "color", "input_hw", "image_hw", "image_offset")
+
     def __init__(self, opt, model, optimizer=None):
         super(PolydetTrainer, self).__init__(opt, model, optimizer=optimizer)
 
@@ -123,9 +127,19 @@ class PolydetTrainer(BaseTrainer):
         object in the sampler, src/lib/datasets/sample/polydet.py:160-405)."""
         if "trans_output" not in batch:
             return batch
-        from ..datasets.sample.polydet import build_inputs, build_targets
+        from ..datasets.sample.polydet import build_inputs, build_inputs_batch, build_targets
         opt = self.opt
-        if "image_u8" in batch:
+        if "image_flat" in batch:
+            # the train loader's ragged batch (collate_ragged): images of any sizes, one launch chain for the batch
+            hw = batch["input_hw"].cpu().numpy()
+            if (hw != hw[0]).any():
+                raise ValueError("the %d images of this batch ask for different network input sizes %s: --keep_res "
+                                 "sizes the input per image, which cannot form one tensor at --batch_size above 1"
+                                 % (hw.shape[0], sorted(set(map(tuple, hw.tolist())))))
+            batch["input"] = build_inputs_batch(batch["image_flat"], batch["image_hw"], batch["image_offset"],
+                                                batch["trans_input"], batch["color"], opt.mean, opt.std,
+                                                int(hw[0][0]), int(hw[0][1]))
+        elif "image_u8" in batch:
             # real datasets: the loader delivered 8-bit images + the drawn augmentation; warp, colour
             # augmentation and normalisation run here (sample/polydet.py:106-136 of the reference)
             hw = batch["input_hw"][0].tolist()

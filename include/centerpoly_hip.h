@@ -661,6 +661,34 @@ int cp_color_aug_normalize(float* img, int64_t HW, int32_t color_on, const int32
 int cp_polydet_post_process(const float* dets, const double* trans_dev, float scale, int32_t B,
                             int32_t K, int32_t ncols, float* out, void* stream);
 
+/* cp_sample_inputs_batch: the image path of the TRAINING sampler for a whole batch whose source images differ in
+ * size (src/lib/datasets/sample/polydet.py:106-136: cv2.warpAffine to input_w x input_h -> `inp / 255.` -> color_aug
+ * -> `(inp - mean) / std` -> CHW; src/lib/utils/image.py:231-264).  The reference warps on the host so that its
+ * collate sees equal shapes; here the 8-bit sources arrive back to back and the dense batch is formed on the device.
+ *   images        DEVICE uint8: the B source images back to back, each [H_b][W_b][3] BGR (already mirrored where flipped)
+ *   image_offset  HOST int64 [B]: byte offset of image b in `images` (64-bit addressing throughout)
+ *   image_hw      HOST int32 [B][2]: (H_b, W_b)
+ *   trans_input   HOST float64 [B][6]: forward affine source -> network input, inverted in float64 as cv::warpAffine does
+ *   color         HOST float64 [B][10]: [on, order x3, alpha x3, light x3], the sampler's row: order = the three ops in
+ *                 application order (0 brightness, 1 contrast, 2 saturation), alpha their blend factors (rounded to
+ *                 float32), light = eig_vec . (eig_val * alpha_pca) per BGR channel.  on == 0: the row is not read
+ *                 further and the image is only normalised
+ *   mean, stdv    HOST float32[3]              out  DEVICE fp32 [B][3][dst_h][dst_w], every element written
+ * Image b of `out` equals, operation for operation, cp_preprocess_warp_normalize(mean 0, std 1) followed by
+ * cp_color_aug_normalize on that image alone: OpenCV's fixed-point 8-bit warp (border 0), x / 255 in float64 cast to
+ * fp32, the grey-level mean over the image's own dst_h x dst_w pixels in float64, the float32 colour chain, the
+ * lighting add in float64, (x - mean) / std in float32.  Only the summation order of the grey mean differs; it is
+ * fixed (no floating-point atomics), so a call repeats its bits and an image's result does not depend on its batch.
+ * Two launches per 16 images; the per-image parameters travel in the kernel arguments (no copy inside the call).
+ * H_b or W_b > 32767 or dst_h > 65535: CP_EUNSUPPORTED.  Null pointers, batch <= 0, a non-positive size, a negative
+ * offset, an order entry outside {0, 1, 2} on a colour-on row, or workspace_bytes below
+ * cp_sample_inputs_workspace_bytes(batch, dst_h, dst_w): CP_EINVAL.  All checks come before any device work. */
+size_t cp_sample_inputs_workspace_bytes(int32_t batch, int32_t dst_h, int32_t dst_w);
+int cp_sample_inputs_batch(const uint8_t* images, const int64_t* image_offset, const int32_t* image_hw,
+                           const double* trans_input, const double* color, const float* mean, const float* stdv,
+                           int32_t batch, int32_t dst_h, int32_t dst_w, float* out, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* soft_nms of external/nms.pyx:77-170 (Cython in the reference) on HOST float32 rows
  * [n][row_stride] (x1,y1,x2,y2,score,...), in place, as merge_outputs uses it
  * (src/lib/detectors/polydet.py:66-67: Nt=0.5, method=2).  method 0 hard / 1 linear /

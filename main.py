@@ -15,10 +15,34 @@ import torch.distributed as dist
 import torch.utils.data
 
 from centerpoly_amd.datasets.dataset_factory import get_dataset
+from centerpoly_amd.datasets.sample.polydet import collate_ragged
 from centerpoly_amd.models.model import create_model, load_model, save_model
 from centerpoly_amd.opts import opts
 from centerpoly_amd.trains.train_factory import train_factory
 from centerpoly_amd.utils.utils import BestMetric
+
+
+def make_train_loader(opt, train_set, per_rank, world=1, rank=0):
+    """The train loader of this rank and its batch sampler (None in one process)."""
+    sampler = None
+    loader_kw = dict(num_workers=opt.num_workers,
+                     # images of one batch may differ in size (KITTI, IDD): they travel back to back and the dense
+                     # batch is formed on the device (PolydetTrainer.prepare_batch -> build_inputs_batch)
+                     collate_fn=collate_ragged,
+                     # pageable batches: 100 MB reach the GPU in 1.9 ms, while host writes into pinned
+                     # staging memory followed by non-blocking copies showed periodic ~90 ms stalls on
+                     # MI355X (tools/probe_stalls.py); the reference pins (main.py:59)
+                     pin_memory=False)
+    if world > 1:
+        # rank r takes chunk_sizes[r] samples of every global batch (even split unless
+        # --master_batch_size says otherwise), no data collective
+        from centerpoly_amd.utils.sampler import ChunkedDistributedSampler
+        sampler = ChunkedDistributedSampler(len(train_set), opt.chunk_sizes, rank, shuffle=True, seed=opt.seed)
+        train_loader = torch.utils.data.DataLoader(train_set, batch_sampler=sampler, **loader_kw)
+    else:
+        train_loader = torch.utils.data.DataLoader(train_set, batch_size=per_rank, shuffle=True, drop_last=True,
+                                                   **loader_kw)
+    return train_loader, sampler
 
 
 def main(opt):
@@ -59,21 +83,7 @@ def main(opt):
         val_loader.dataset.run_eval(preds, opt.save_dir)
         return
     train_set = Dataset(opt, "train")
-    sampler = None
-    loader_kw = dict(num_workers=opt.num_workers,
-                     # pageable batches: 100 MB reach the GPU in 1.9 ms, while host writes into pinned
-                     # staging memory followed by non-blocking copies showed periodic ~90 ms stalls on
-                     # MI355X (tools/probe_stalls.py); the reference pins (main.py:59)
-                     pin_memory=False)
-    if world > 1:
-        # rank r takes chunk_sizes[r] samples of every global batch (even split unless
-        # --master_batch_size says otherwise), no data collective
-        from centerpoly_amd.utils.sampler import ChunkedDistributedSampler
-        sampler = ChunkedDistributedSampler(len(train_set), opt.chunk_sizes, rank, shuffle=True, seed=opt.seed)
-        train_loader = torch.utils.data.DataLoader(train_set, batch_sampler=sampler, **loader_kw)
-    else:
-        train_loader = torch.utils.data.DataLoader(train_set, batch_size=per_rank, shuffle=True, drop_last=True,
-                                                   **loader_kw)
+    train_loader, sampler = make_train_loader(opt, train_set, per_rank, world, rank)
     if rank == 0:
         os.makedirs(opt.save_dir, exist_ok=True)
     print("Starting training...")
