@@ -13,26 +13,25 @@
 //   cp_annot_id_instances  one pass over the id image, a run of 16 pixels per lane, integer min / max atomics into a
 //                          box table of 65536 entries (a plain read first: a bound that cannot improve the table is
 //                          not sent); one workgroup then compacts the table in ascending value.
-//   cp_polygon_masks       F \ O of class_masks.hip for polygons of up to 4096 vertices: the edges once into the
-//                          workspace; one workgroup per (polygon, row) collects the row's crossings in LDS (the
-//                          arithmetic is class_masks_core.h, unchanged), sorts them there and writes the spans; one
-//                          lane per edge clears PIL's integer line; the counts.
+//   cp_polygon_masks       F \ O of class_masks.hip for polygons of up to 4096 vertices, the workgroup form of
+//                          scanline.h: the edges once into the workspace; one workgroup per (polygon, row) collects
+//                          the row's crossings in LDS, sorts them there and writes the spans; one lane per edge
+//                          clears PIL's integer line; the counts.
 //   cp_annot_rays_*        one wave per ray: 64 consecutive steps of the line per iteration from the closed form of
 //                          the package's error term, a 64-bit ballot and its first set bit for the hit.
 // Integers and correctly rounded float64 / float32 operations with no contraction: the same bits on every run.
 #include "cp_common.h"
-#include "class_masks_core.h"
+#include "scanline.h"
 
 namespace {
 
 constexpr int kMaxInst = 1024;                                            // objects of one id image, rays' boxes
 constexpr int kMaxClasses = 32;
 constexpr int kMaxPolys = 128;                                            // polygons of one cp_polygon_masks call
-constexpr int kMaxPolyVerts = 4096;
+constexpr int kMaxPolyVerts = kSlMaxGroupVerts;
 constexpr int kMaxRayVerts = 64;
 constexpr int kIdValues = 65536;
 constexpr int kRun = 16;                                                  // pixels of one lane in the id pass
-constexpr float kNone = __builtin_inff();                                 // "no crossing": sorts behind every value
 
 // ---------------------------------------------------------------------------------------------- id instances ----
 
@@ -146,93 +145,22 @@ struct PolyMaskArgs {
 };
 
 __global__ __launch_bounds__(256) void poly_edges_kernel(PolyMaskArgs a) {
-  __shared__ int s_lo[4], s_hi[4];
-  const int i = blockIdx.x, t = threadIdx.x;
-  const int base = a.first[i], N = a.first[i + 1] - base;
-  const int* p = a.xy + 2ll * base;
-  int lo = INT32_MAX, hi = INT32_MIN;
-  for (int k = t; k < N; k += 256) {
-    a.edges[base + k] = cm_make_edge(p, k, N);
-    const int y = p[2 * k + 1];
-    lo = min(lo, y); hi = max(hi, y);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = min(lo, __shfl_xor(lo, o, 64));
-    hi = max(hi, __shfl_xor(hi, o, 64));
-  }
-  if ((t & 63) == 0) { s_lo[t >> 6] = lo; s_hi[t >> 6] = hi; }
-  __syncthreads();
-  if (t == 0) {
-    a.yrange[2 * i + 0] = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
-    a.yrange[2 * i + 1] = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
-  }
+  const int i = blockIdx.x, base = a.first[i];
+  sl_group_edges(a.xy + 2ll * base, a.first[i + 1] - base, a.edges + base, a.yrange + 2 * i);
 }
 
-// The row's sorted crossing list and then its flat edges share one LDS array: an edge gives at most two crossings,
-// or, when it is flat, one span of two integers.  The masks were zeroed before: only spans are written.
+// One row of one polygon (sl_group_row).  The masks were zeroed before: only spans are written.
 __global__ __launch_bounds__(256) void poly_fill_kernel(PolyMaskArgs a) {
   __shared__ float s_x[2 * kMaxPolyVerts];
   __shared__ int s_n;
-  const int i = blockIdx.y, y = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int i = blockIdx.y, y = blockIdx.x;
   const int ylo = a.yrange[2 * i], yhi = a.yrange[2 * i + 1];
   if (y < ylo || y > yhi) return;                                         // uniform in the workgroup
   const int base = a.first[i], N = a.first[i + 1] - base;
   const CmEdge* edges = a.edges + base;
   const int last_row = min(max(yhi, 0), a.H);
   unsigned char* row = a.masks + ((long long)i * a.H + y) * a.W;
-  if (t == 0) s_n = 0;
-  __syncthreads();
-  for (int k = t; k < N; k += 256) {
-    float out[2];
-    const int c = cm_crossings([&](int j) { return edges[j]; }, k, y, last_row, out);
-    if (c) {
-      const int at = atomicAdd(&s_n, c);
-      s_x[at] = out[0];
-      if (c == 2) s_x[at + 1] = out[1];
-    }
-  }
-  __syncthreads();
-  const int cnt = s_n;
-  int P = 2;
-  while (P < cnt) P <<= 1;
-  for (int k = cnt + t; k < P; k += 256) s_x[k] = kNone;
-  __syncthreads();
-  for (int k = 2; k <= P; k <<= 1)                                        // bitonic sort, ascending
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int q = t; q < P; q += 256) {
-        const int o = q ^ j;
-        if (o > q) {
-          const float u = s_x[q], v = s_x[o];
-          if ((u > v) == ((q & k) == 0)) { s_x[q] = v; s_x[o] = u; }
-        }
-      }
-      __syncthreads();
-    }
-  for (int s = w; 2 * s + 1 < cnt; s += 4) {                              // one wave per span
-    const int lo = max(cm_round_up(s_x[2 * s]), 0), hi = min(cm_round_down(s_x[2 * s + 1]), a.W - 1);
-    for (int x = lo + lane; x <= hi; x += 64) row[x] = 255;
-  }
-  __syncthreads();
-  if (t == 0) s_n = 0;
-  __syncthreads();
-  int* s_flat = reinterpret_cast<int*>(s_x);
-  for (int k = t; k < N; k += 256) {
-    const CmEdge e = edges[k];
-    if (e.kind == CM_FLAT && e.ymin == y) {
-      const int lo = max(e.xmin, 0), hi = min(e.xmax, a.W - 1);
-      if (lo <= hi) {
-        const int at = atomicAdd(&s_n, 1);
-        s_flat[2 * at] = lo; s_flat[2 * at + 1] = hi;
-      }
-    }
-  }
-  __syncthreads();
-  const int nflat = s_n;
-  for (int s = w; s < nflat; s += 4) {
-    const int lo = s_flat[2 * s], hi = s_flat[2 * s + 1];
-    for (int x = lo + lane; x <= hi; x += 64) row[x] = 255;
-  }
+  sl_group_row(edges, N, y, last_row, a.W, s_x, &s_n, [&](int x) { row[x] = 255; });
 }
 
 // PIL's integer line of every edge, the part on the canvas, cleared (outline=0 after fill=255)
@@ -243,29 +171,8 @@ __global__ __launch_bounds__(64) void poly_outline_kernel(PolyMaskArgs a) {
   const int* p = a.xy + 2ll * base;
   const int j = k + 1 == N ? 0 : k + 1;
   const int x0 = p[2 * k], y0 = p[2 * k + 1], x1 = p[2 * j], y1 = p[2 * j + 1];
-  const long long steps = cm_line_steps(x0, y0, x1, y1);
-  if (steps < 0) return;
-  const long long dx = (long long)x1 - x0, dy = (long long)y1 - y0;
-  const long long ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
-  const bool xmajor = ax > ay;
-  const long long c0 = xmajor ? x0 : y0, size = xmajor ? a.W : a.H;
-  const bool fwd = (xmajor ? dx : dy) >= 0;
-  long long t0 = fwd ? -c0 : c0 - (size - 1), t1 = fwd ? size - 1 - c0 : c0;
-  t0 = t0 < 0 ? 0 : t0;
-  t1 = t1 > steps ? steps : t1;
-  if (t0 > t1) return;
-  const long long dmaj = xmajor ? ax : ay, dmin = xmajor ? ay : ax;
-  long long m = (2 * dmin * t0 + dmaj) / (2 * dmaj);
-  long long r = (2 * dmin * t0 + dmaj) - m * (2 * dmaj);
-  const int smaj = fwd ? 1 : -1, smin = (xmajor ? dy : dx) < 0 ? -1 : 1;
-  const long long o0 = xmajor ? y0 : x0, osize = xmajor ? a.H : a.W;
   unsigned char* mk = a.masks + (long long)i * a.H * a.W;
-  for (long long s = t0; s <= t1; ++s) {
-    const long long cmaj = c0 + smaj * s, cmin = o0 + smin * m;
-    if (cmin >= 0 && cmin < osize) mk[xmajor ? cmin * a.W + cmaj : cmaj * a.W + cmin] = 0;
-    r += 2 * dmin;
-    if (r >= 2 * dmaj) { r -= 2 * dmaj; m += 1; }
-  }
+  sl_line_clipped(x0, y0, x1, y1, a.W, a.H, [&](long long at) { mk[at] = 0; });
 }
 
 __global__ __launch_bounds__(256) void poly_count_kernel(PolyMaskArgs a) {

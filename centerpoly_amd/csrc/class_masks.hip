@@ -10,7 +10,8 @@
 // (PIL draws no outline whose ink equals the fill's, so the second call clears F alone: an instance loses its own
 // outline but hides farther ones with its fill only).
 // There is no contour band here that would hide the difference between PIL's scan-line fill and an even-odd test at
-// pixel centres (see result_writer.hip), so F and O are PIL's own rules (class_masks_core.h).  Three kernels and one
+// pixel centres (see result_writer.hip), so F and O are PIL's own rules (class_masks_core.h; scanline.h holds the scan
+// line around them, here in its wave form, and the clipped line).  Three kernels and one
 // small memset whatever n is; every mask byte is written once by the fill kernel and swept once by the last one:
 //   fill kernel     one wave per (instance, row): lane k owns edge k and computes what it adds to the row's crossing
 //                   list in float32 (the vertex rule walks the earlier edges in LDS); a bitonic sort of the at most
@@ -21,15 +22,13 @@
 //                   unless an earlier occluding instance of the group filled the pixel (bit 0), 2 and 3 become 0;
 //                   the counts.
 #include "cp_common.h"
-#include "class_masks_core.h"
-#include "wave_sort.h"
+#include "scanline.h"
 
 namespace {
 
 constexpr int kMaxInst = 128;
 constexpr int kMaxVerts = 64;
 constexpr int kRowsPerBlock = 4;                                          // waves of the fill kernel's workgroup
-constexpr float kNone = __builtin_inff();                                 // "no crossing": sorts behind every value
 
 struct ClassMaskArgs {
   const int* poly;            // [n][N][2] (x, y), drawing order
@@ -40,13 +39,12 @@ struct ClassMaskArgs {
   int n, N, H, W;
 };
 
-struct Span { int lo, hi; };
 struct Bytes16 { unsigned w[4]; };
 
 __global__ __launch_bounds__(64 * kRowsPerBlock) void class_fill_kernel(ClassMaskArgs a) {
   __shared__ CmEdge s_edge[kMaxVerts];
   __shared__ float s_x[kRowsPerBlock][2 * kMaxVerts];
-  __shared__ Span s_span[kRowsPerBlock][2 * kMaxVerts];
+  __shared__ SlSpan s_span[kRowsPerBlock][2 * kMaxVerts];
   const int i = blockIdx.y, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int y = blockIdx.x * kRowsPerBlock + w;
   const int* p = a.poly + (long long)i * a.N * 2;
@@ -64,41 +62,13 @@ __global__ __launch_bounds__(64 * kRowsPerBlock) void class_fill_kernel(ClassMas
   const int last_row = min(hi, a.H);
   __syncthreads();
 
-  float out[2] = {kNone, kNone};
-  const int c = cm_crossings([&](int j) { return s_edge[j]; }, lane, y, last_row, out);
-  float xa = c >= 1 ? out[0] : kNone, xb = c == 2 ? out[1] : kNone;
-  const int cnt = __popcll(__ballot(c >= 1)) + __popcll(__ballot(c == 2));
-  wave_sort128(xa, xb, lane);
-  s_x[w][lane] = xa;
-  s_x[w][lane + 64] = xb;
-  __syncthreads();
-
-  // spans: pair s of the sorted crossings, then the flat edges of this row; clipped, empty ones dropped
-  const unsigned long long below = (1ull << lane) - 1ull;
-  Span sp;
-  sp.lo = 1; sp.hi = 0;
-  if (2 * lane + 1 < cnt) {
-    sp.lo = max(cm_round_up(s_x[w][2 * lane]), 0);
-    sp.hi = min(cm_round_down(s_x[w][2 * lane + 1]), a.W - 1);
-  }
-  const unsigned long long m1 = __ballot(sp.lo <= sp.hi);
-  if (sp.lo <= sp.hi) s_span[w][__popcll(m1 & below)] = sp;
-  const CmEdge e = s_edge[lane];
-  Span fl;
-  fl.lo = 1; fl.hi = 0;
-  if (e.kind == CM_FLAT && e.ymin == y) { fl.lo = max(e.xmin, 0); fl.hi = min(e.xmax, a.W - 1); }
-  const unsigned long long m2 = __ballot(fl.lo <= fl.hi);
-  const int n1 = __popcll(m1);
-  if (fl.lo <= fl.hi) s_span[w][n1 + __popcll(m2 & below)] = fl;
-  const int nsp = n1 + __popcll(m2);
-  __syncthreads();
-
+  const int nsp = sl_wave_spans(s_edge, s_x[w], s_span[w], lane, y, last_row, a.W);
   if (y >= a.H) return;
   unsigned char* row = a.masks + ((long long)i * a.H + y) * a.W;
   for (int x0 = lane * 16; x0 < a.W; x0 += 64 * 16) {
     unsigned bits = 0;
     for (int s = 0; s < nsp; ++s) {
-      const Span q = s_span[w][s];
+      const SlSpan q = s_span[w][s];
       const int lo = max(q.lo, x0) - x0, hi2 = min(q.hi, x0 + 15) - x0;
       if (lo <= hi2) bits |= ((2u << hi2) - 1u) & ~((1u << lo) - 1u);
     }
@@ -121,32 +91,9 @@ __global__ __launch_bounds__(64) void class_outline_kernel(ClassMaskArgs a) {
   const int* p = a.poly + (long long)i * a.N * 2;
   const int j = k + 1 == a.N ? 0 : k + 1;
   const int x0 = p[2 * k], y0 = p[2 * k + 1], x1 = p[2 * j], y1 = p[2 * j + 1];
-  const long long steps = cm_line_steps(x0, y0, x1, y1);
-  if (steps < 0) return;
-  // the steps whose coordinate along the longer axis is on the canvas (far-away vertices: nothing is walked there)
-  const long long dx = (long long)x1 - x0, dy = (long long)y1 - y0;
-  const long long ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
-  const bool xmajor = ax > ay;
-  const long long c0 = xmajor ? x0 : y0, size = xmajor ? a.W : a.H;
-  const bool fwd = (xmajor ? dx : dy) >= 0;
-  long long t0 = fwd ? -c0 : c0 - (size - 1), t1 = fwd ? size - 1 - c0 : c0;
-  t0 = t0 < 0 ? 0 : t0;
-  t1 = t1 > steps ? steps : t1;
-  if (t0 > t1) return;
-  // the other coordinate at step t0 from the closed form, then its error term step by step (cm_line_pixel)
-  const long long dmaj = xmajor ? ax : ay, dmin = xmajor ? ay : ax;
-  long long m = (2 * dmin * t0 + dmaj) / (2 * dmaj);
-  long long r = (2 * dmin * t0 + dmaj) - m * (2 * dmaj);
-  const int smaj = fwd ? 1 : -1, smin = (xmajor ? dy : dx) < 0 ? -1 : 1;
-  const long long o0 = xmajor ? y0 : x0, osize = xmajor ? a.H : a.W;
   unsigned char* mk = a.masks + (long long)i * a.H * a.W;
-  for (long long s = t0; s <= t1; ++s) {
-    const long long cmaj = c0 + smaj * s, cmin = o0 + smin * m;
-    if (cmin >= 0 && cmin < osize) mk[xmajor ? cmin * a.W + cmaj : cmaj * a.W + cmin] |= 2;   // (edges that meet
-                                                                          // store the same byte: fill bit | 2)
-    r += 2 * dmin;
-    if (r >= 2 * dmaj) { r -= 2 * dmaj; m += 1; }
-  }
+  // (edges that meet store the same byte: fill bit | 2)
+  sl_line_clipped(x0, y0, x1, y1, a.W, a.H, [&](long long at) { mk[at] |= 2; });
 }
 
 // four pixels per word, every byte bit 0 = filled, bit 1 = on the outline

@@ -8,25 +8,24 @@
 // where there is none.  A polygon of two vertices (a, b) has the edges a -> b and b -> a, as PIL builds them: F of
 // (a, b, a).
 //
-//   paint_edges_kernel   one workgroup per polygon: the edge table (class_masks_core.h, unchanged) and the polygon's
-//                        smallest and largest y, once.
+//   paint_edges_kernel   one workgroup per polygon: the edge table and the polygon's smallest and largest y, once
+//                        (sl_group_edges of scanline.h).
 //   paint_rows_kernel    the drawing order is a dependency, so a row belongs to exactly one workgroup.  It holds the
 //                        row (W int32, at most 64 KB) in LDS, walks the polygons in order, skips those whose y-range
-//                        misses the row, and for each of the others collects the row's crossings in LDS, sorts them
-//                        there (poly_fill_kernel's bitonic network) and overwrites the spans and the flat edges of the
+//                        misses the row, and for each of the others runs the workgroup form's row pass (sl_group_row:
+//                        crossings collected and sorted in LDS), which overwrites the spans and the flat edges of the
 //                        row in the LDS image.  The row goes to memory once, coalesced.
 // No atomics on memory, no read-modify-write of the image, two launches and one copy of `first` whatever n is.
 // Integers and float32 with no contraction: the same bits on every run.
 #include "cp_common.h"
-#include "class_masks_core.h"
+#include "scanline.h"
 
 namespace {
 
 constexpr int kMaxPaintPolys = 4096;
-constexpr int kMaxPaintVerts = 4096;                                      // of one polygon
+constexpr int kMaxPaintVerts = kSlMaxGroupVerts;                          // of one polygon
 constexpr int kMaxPaintTotal = 1 << 20;                                   // of all polygons
 constexpr int kMaxPaintWidth = 16384;                                     // the row image: 64 KB of LDS
-constexpr float kPaintNone = __builtin_inff();                            // "no crossing": sorts behind every value
 
 struct PaintArgs {
   const int* xy;              // [T][2]
@@ -39,38 +38,19 @@ struct PaintArgs {
 };
 
 __global__ __launch_bounds__(256) void paint_edges_kernel(PaintArgs a) {
-  __shared__ int s_lo[4], s_hi[4];
-  const int i = blockIdx.x, t = threadIdx.x;
-  const int base = a.first[i], N = a.first[i + 1] - base;
-  const int* p = a.xy + 2ll * base;
-  int lo = INT32_MAX, hi = INT32_MIN;
-  for (int k = t; k < N; k += 256) {
-    // N == 2: a -> b, then the closing edge b -> a (absent only when a == b, where a -> b is the one flat pixel)
-    a.edges[base + k] = cm_make_edge(p, k, N);
-    const int y = p[2 * k + 1];
-    lo = min(lo, y); hi = max(hi, y);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = min(lo, __shfl_xor(lo, o, 64));
-    hi = max(hi, __shfl_xor(hi, o, 64));
-  }
-  if ((t & 63) == 0) { s_lo[t >> 6] = lo; s_hi[t >> 6] = hi; }
-  __syncthreads();
-  if (t == 0) {
-    a.yrange[2 * i + 0] = min(min(s_lo[0], s_lo[1]), min(s_lo[2], s_lo[3]));
-    a.yrange[2 * i + 1] = max(max(s_hi[0], s_hi[1]), max(s_hi[2], s_hi[3]));
-  }
+  // N == 2: a -> b, then the closing edge b -> a (absent only when a == b, where a -> b is the one flat pixel)
+  const int i = blockIdx.x, base = a.first[i];
+  sl_group_edges(a.xy + 2ll * base, a.first[i + 1] - base, a.edges + base, a.yrange + 2 * i);
 }
 
-// s_x: the row's crossing list of the current polygon (an edge gives at most two), then its flat edges (one span of two
-// integers each).  s_row: the row as painted so far, W <= kWidth int32.  Every index into s_row is cut to 0 .. W-1.
+// s_x, s_n: sl_group_row's list and counter for the current polygon.  s_row: the row as painted so far, W <= kWidth
+// int32.  Every index into s_row is cut to 0 .. W-1.
 template <int kWidth>
 __global__ __launch_bounds__(256) void paint_rows_kernel(PaintArgs a) {
   __shared__ int s_row[kWidth];
   __shared__ float s_x[2 * kMaxPaintVerts];
-  __shared__ int s_n, s_nflat;
-  const int y = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  __shared__ int s_n;
+  const int y = blockIdx.x, t = threadIdx.x;
   for (int x = t; x < a.W; x += 256) s_row[x] = a.background;
   for (int i = 0; i < a.n; ++i) {
     const int ylo = a.yrange[2 * i], yhi = a.yrange[2 * i + 1];
@@ -80,56 +60,7 @@ __global__ __launch_bounds__(256) void paint_rows_kernel(PaintArgs a) {
     const int last_row = min(max(yhi, 0), a.H);
     const int v = a.value[i];
     __syncthreads();                                                      // the previous polygon is done with s_x
-    if (t == 0) { s_n = 0; s_nflat = 0; }
-    __syncthreads();
-    for (int k = t; k < N; k += 256) {
-      float out[2];
-      const int c = cm_crossings([&](int j) { return edges[j]; }, k, y, last_row, out);
-      if (c) {
-        const int at = atomicAdd(&s_n, c);                                // LDS; the list is sorted below
-        s_x[at] = out[0];
-        if (c == 2) s_x[at + 1] = out[1];
-      }
-    }
-    __syncthreads();
-    const int cnt = s_n;
-    int P = 2;
-    while (P < cnt) P <<= 1;
-    for (int k = cnt + t; k < P; k += 256) s_x[k] = kPaintNone;
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)                                      // bitonic sort, ascending
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int q = t; q < P; q += 256) {
-          const int o = q ^ j;
-          if (o > q) {
-            const float u = s_x[q], z = s_x[o];
-            if ((u > z) == ((q & k) == 0)) { s_x[q] = z; s_x[o] = u; }
-          }
-        }
-        __syncthreads();
-      }
-    for (int s = w; 2 * s + 1 < cnt; s += 4) {                            // one wave per span
-      const int lo = max(cm_round_up(s_x[2 * s]), 0), hi = min(cm_round_down(s_x[2 * s + 1]), a.W - 1);
-      for (int x = lo + lane; x <= hi; x += 64) s_row[x] = v;
-    }
-    __syncthreads();
-    int* s_flat = reinterpret_cast<int*>(s_x);
-    for (int k = t; k < N; k += 256) {
-      const CmEdge e = edges[k];
-      if (e.kind == CM_FLAT && e.ymin == y) {
-        const int lo = max(e.xmin, 0), hi = min(e.xmax, a.W - 1);
-        if (lo <= hi) {
-          const int at = atomicAdd(&s_nflat, 1);                          // the same value everywhere: any order
-          s_flat[2 * at] = lo; s_flat[2 * at + 1] = hi;
-        }
-      }
-    }
-    __syncthreads();
-    const int nflat = s_nflat;
-    for (int s = w; s < nflat; s += 4) {
-      const int lo = s_flat[2 * s], hi = s_flat[2 * s + 1];
-      for (int x = lo + lane; x <= hi; x += 64) s_row[x] = v;
-    }
+    sl_group_row(edges, N, y, last_row, a.W, s_x, &s_n, [&](int x) { s_row[x] = v; });
   }
   __syncthreads();
   int* row = a.image + (long long)y * a.W;

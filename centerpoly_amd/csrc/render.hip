@@ -7,8 +7,8 @@
 // max-reduction per pixel and one compose pass: integer arithmetic, order independent, the same bits on every run.
 //   memset           the operation map (4 bytes per pixel: 8 * paint index + operation, 0 = untouched);
 //   raster kernel    one workgroup per (instance, band of 16 rows); a workgroup whose band meets nothing of its
-//                    instance returns at once.  Fill: one wave per row, PIL's scan line exactly as class_masks.hip has
-//                    it (class_masks_core.h: lane k owns edge k, the crossings sorted through wave shuffles), the spans
+//                    instance returns at once.  Fill: one wave per row, PIL's scan line in the wave form of scanline.h
+//                    (lane k owns edge k, the crossings sorted through wave shuffles), the spans
 //                    painted with atomicMax.  Outline: PIL's integer line, edge by edge, the on-canvas steps of an edge that
 //                    can reach the band spread over the workgroup, each pixel dilated by the (2r+1)^2 square.  Box frame,
 //                    label background and glyph cells: rectangles spread over the workgroup;
@@ -18,8 +18,7 @@
 //
 // cp_render_heatmap is the reference's gen_colormap + add_blend_img on the device in one launch.
 #include "cp_common.h"
-#include "class_masks_core.h"
-#include "wave_sort.h"
+#include "scanline.h"
 
 namespace {
 
@@ -34,7 +33,6 @@ constexpr int kMaxCoord = 1 << 29;                                        // ver
 constexpr int kWaves = 4;                                                 // waves of the raster workgroup
 constexpr int kBand = 16;                                                 // rows of a band (a multiple of kWaves)
 constexpr int kCellW = 6, kCellH = 11;                                    // a glyph cell
-constexpr float kNone = __builtin_inff();                                 // "no crossing": sorts behind every value
 
 enum { OP_FILL = 1, OP_OUTLINE = 2, OP_BOX = 3, OP_LABEL_BG = 4, OP_GLYPH = 5 };
 
@@ -53,8 +51,6 @@ struct OverlayArgs {
   int alpha, radius, thick, white, show_txt, show_poly;
   unsigned char outline[3];
 };
-
-struct Span { int lo, hi; };
 
 // a box coordinate: the float truncated toward zero, kept inside int32 (a NaN is 0)
 __device__ __forceinline__ int box_int(float f) {
@@ -85,7 +81,7 @@ __device__ __forceinline__ void paint_rect(const OverlayArgs& a, long long xlo, 
 __global__ __launch_bounds__(64 * kWaves) void overlay_raster_kernel(OverlayArgs a) {
   __shared__ CmEdge s_edge[kMaxVerts];
   __shared__ float s_x[kWaves][2 * kMaxVerts];
-  __shared__ Span s_span[kWaves][2 * kMaxVerts];
+  __shared__ SlSpan s_span[kWaves][2 * kMaxVerts];
   const int n = a.n[0], i = blockIdx.y;
   if (n > kMaxInst || n > a.R || i >= n) return;                          // (uniform in the workgroup, as all below)
   const int s = a.src[i];
@@ -127,7 +123,7 @@ __global__ __launch_bounds__(64 * kWaves) void overlay_raster_kernel(OverlayArgs
   const bool label_here = len > 0 && ly0 <= ye && ly1 >= yb;
   if (!(fill_here || line_here || box_here || label_here)) return;
 
-  // ---- 1: fill, PIL's scan line (class_masks.hip's fill kernel, painting spans instead of writing the row) ----
+  // ---- 1: fill, PIL's scan line (sl_wave_spans), the spans painted ----
   if (fill_here) {
     if (tid < kMaxVerts) {
       CmEdge e;
@@ -138,36 +134,11 @@ __global__ __launch_bounds__(64 * kWaves) void overlay_raster_kernel(OverlayArgs
     __syncthreads();
     for (int it = 0; it < kBand / kWaves; ++it) {
       const int y = yb + it * kWaves + w;
-      float out[2] = {kNone, kNone};
-      const int c = cm_crossings([&](int j) { return s_edge[j]; }, lane, y, last_row, out);
-      float xa = c >= 1 ? out[0] : kNone, xb = c == 2 ? out[1] : kNone;
-      const int cnt = __popcll(__ballot(c >= 1)) + __popcll(__ballot(c == 2));
-      wave_sort128(xa, xb, lane);
-      s_x[w][lane] = xa;
-      s_x[w][lane + 64] = xb;
-      __syncthreads();
-      const unsigned long long below = (1ull << lane) - 1ull;
-      Span sp;
-      sp.lo = 1; sp.hi = 0;
-      if (2 * lane + 1 < cnt) {
-        sp.lo = max(cm_round_up(s_x[w][2 * lane]), 0);
-        sp.hi = min(cm_round_down(s_x[w][2 * lane + 1]), a.W - 1);
-      }
-      const unsigned long long m1 = __ballot(sp.lo <= sp.hi);
-      if (sp.lo <= sp.hi) s_span[w][__popcll(m1 & below)] = sp;
-      const CmEdge e = s_edge[lane];
-      Span fl;
-      fl.lo = 1; fl.hi = 0;
-      if (e.kind == CM_FLAT && e.ymin == y) { fl.lo = max(e.xmin, 0); fl.hi = min(e.xmax, a.W - 1); }
-      const unsigned long long m2 = __ballot(fl.lo <= fl.hi);
-      const int n1 = __popcll(m1);
-      if (fl.lo <= fl.hi) s_span[w][n1 + __popcll(m2 & below)] = fl;
-      const int nsp = n1 + __popcll(m2);
-      __syncthreads();
+      const int nsp = sl_wave_spans(s_edge, s_x[w], s_span[w], lane, y, last_row, a.W);
       if (y <= ye) {
         unsigned* mrow = a.map + (long long)y * a.W;
         for (int q = 0; q < nsp; ++q) {
-          const Span v = s_span[w][q];                                    // inside [0, W - 1] by construction
+          const SlSpan v = s_span[w][q];                                  // inside [0, W - 1] by construction
           for (int x = v.lo + lane; x <= v.hi; x += 64) atomicMax(mrow + x, base | OP_FILL);
         }
       }

@@ -1,5 +1,5 @@
 // A bitonic sort of 128 float32 values held two per lane across one 64-lane wave, through wave shuffles: what the
-// scan-line rasterisers (class_masks.hip, render.hip) order a row's crossing list with.
+// wave form of the scan line (scanline.h) orders a row's crossing list with.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,11 +1,12 @@
 """cp_class_instance_masks / cp_class_writer_instances: the KITTI and IDD writers' masks and selection.
 
 The fixtures (tests/golden/class_writer_*.npz) were drawn by PIL itself through the reference's two loops
-(tests/golden/gen_class_writer_golden.py).  `pil_fill` / `pil_outline` below are a line-by-line transcription of
-centerpoly_amd/csrc/class_masks_core.h, the rules the kernels run: the CPU test holds them against the installed PIL
-on seeded random polygons (zero differing pixels), the GPU tests hold the kernels against the fixtures and against
-the transcription."""
+(tests/golden/gen_class_writer_golden.py).  `pil_fill` / `pil_outline` are tests/golden/pil_scanline_host.py, a
+transcription of centerpoly_amd/csrc/class_masks_core.h, the rules the kernels run: the CPU test holds them against
+the installed PIL on seeded random polygons (zero differing pixels), the GPU tests hold the kernels against the
+fixtures and against the transcription."""
 import ctypes
+import functools
 import os
 import types
 
@@ -13,6 +14,7 @@ import numpy as np
 import pytest
 
 from centerpoly_amd import _C
+from pil_scanline_host import fill as pil_fill, outline as pil_outline
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CASES = ["kitti_a", "kitti_b", "idd_a", "idd_b", "odd"]
@@ -40,92 +42,10 @@ def _dataset(z, thresh=None):
     return ds
 
 
-# ------------------------------------------------------------------- class_masks_core.h, transcribed ------------
-def _round_up(f):
-    f = f32(f)
-    return int(np.floor(f + f32(0.5))) if f >= 0 else -int(np.floor(abs(f) + f32(0.5)))
-
-
-def _round_down(f):
-    f = f32(f)
-    return int(np.ceil(f - f32(0.5))) if f >= 0 else -int(np.ceil(abs(f) - f32(0.5)))
-
-
-def _edges(pts):
-    """cm_make_edge for every k: (kind, x0, y0, ymin, ymax, xmin, xmax, dx); kind 0 absent, 1 flat, 2 sloped."""
-    N, out = len(pts), []
-    for k in range(N):
-        (x0, y0), (x1, y1) = pts[k], pts[(k + 1) % N]
-        kind = 0 if (k + 1 == N and (x0, y0) == (x1, y1)) else 1 if y0 == y1 else 2
-        dx = f32(x1 - x0) / f32(y1 - y0) if kind == 2 else f32(0)
-        out.append((kind, x0, y0, min(y0, y1), max(y0, y1), min(x0, x1), max(x0, x1), dx))
-    return out
-
-
-def _x_at(e, y):
-    return f32(f32(y - e[2]) * e[7]) + f32(e[1])
-
-
-def _crossings(E, k, y, last_row):
-    e = E[k]
-    if e[0] != 2 or y < e[3] or y > e[4]:
-        return []
-    x = _x_at(e, y)
-    if y == e[4] and y < last_row:
-        return [x, x]
-    if (y == e[3] or y == e[4]) and e[7] != 0:
-        for j in range(k):
-            o = E[j]
-            if o[0] != 2 or o[7] == 0:
-                continue
-            if not ((y == e[3] and y == o[3]) or (y == e[4] and y == o[4])):
-                continue
-            if np.rint(x) != np.rint(_x_at(o, y)):
-                continue
-            if (e[7] > 0) == (o[7] > 0):
-                adj = y - 1 if y == last_row else y + 1
-                a, b = _x_at(e, adj), _x_at(o, adj)
-                if (y == e[4]) != (e[7] > 0):
-                    x = max(f32(_round_up(min(a, b)) - 1), x)
-                else:
-                    x = min(f32(_round_up(max(a, b)) + 1), x)
-            break
-    return [x]
-
-
-def pil_fill(pts, W, H):
-    pts = [tuple(int(v) for v in p) for p in pts]
-    m = np.zeros((H, W), bool)
-    E = _edges(pts)
-    last_row = min(max(0, max(p[1] for p in pts)), H)
-    for y in range(max(0, min(p[1] for p in pts)), min(H - 1, last_row) + 1):
-        xx = sorted(v for k in range(len(E)) for v in _crossings(E, k, y, last_row))
-        spans = [(_round_up(xx[i - 1]), _round_down(xx[i])) for i in range(1, len(xx), 2)]
-        spans += [(e[5], e[6]) for e in E if e[0] == 1 and e[3] == y]
-        for lo, hi in spans:
-            lo, hi = max(lo, 0), min(hi, W - 1)
-            if lo <= hi:
-                m[y, lo:hi + 1] = True
-    return m
-
-
-def pil_outline(pts, W, H):
-    pts = [tuple(int(v) for v in p) for p in pts]
-    m = np.zeros((H, W), bool)
-    for k in range(len(pts)):
-        (x0, y0), (x1, y1) = pts[k], pts[(k + 1) % len(pts)]
-        ax, ay = abs(x1 - x0), abs(y1 - y0)
-        if ax == 0 and ay == 0:
-            continue
-        sx, sy = (1 if x1 >= x0 else -1), (1 if y1 >= y0 else -1)
-        t = np.arange(max(ax, ay) + 1, dtype=np.int64)
-        if ax > ay:
-            px, py = x0 + sx * t, y0 + sy * ((2 * ay * t + ax) // (2 * ax))
-        else:
-            px, py = x0 + sx * ((2 * ax * t + ay) // (2 * ay)), y0 + sy * t
-        ok = (px >= 0) & (px < W) & (py >= 0) & (py < H)
-        m[py[ok], px[ok]] = True
-    return m
+@functools.lru_cache(maxsize=None)
+def _fill_outline(pts, W, H):
+    """(F, O) of the polygon `pts`, a tuple of (x, y): computed once, shared by the tests, never written to."""
+    return pil_fill(pts, W, H), pil_outline(pts, W, H)
 
 
 def host_masks(polys, groups, flags, W, H):
@@ -135,7 +55,7 @@ def host_masks(polys, groups, flags, W, H):
         if not fl & 1:
             out.append(np.zeros((H, W), np.uint8))
             continue
-        F, O = pil_fill(pts, W, H), pil_outline(pts, W, H)
+        F, O = _fill_outline(tuple(pts), W, H)
         rem = removed.setdefault(g, np.zeros((H, W), bool))
         out.append(((F & ~O & ~rem) * 255).astype(np.uint8))
         if fl & 2:
@@ -297,15 +217,20 @@ def test_masks_equal_the_fixtures(name):
     assert np.array_equal(m2.cpu().numpy(), masks) and np.array_equal(c2.cpu().numpy(), counts)
 
 
+def _random_instances(rng, W, H, N):
+    polys = []
+    for t in range(128):
+        pts = _random_polygon(rng, t, W, H)
+        polys.append((pts * N)[:N] if len(pts) < N else pts[:N])             # N vertices: the polygon walked again
+    return polys
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("W,H,N,seed", [(97, 61, 16, 0), (64, 48, 7, 1), (33, 130, 64, 2), (2, 3, 3, 3)])
 def test_masks_equal_the_transcription_on_random_polygons(W, H, N, seed):
     """Beyond the fixtures, without PIL: 128 random instances a call, groups interleaved, some not drawn."""
     rng = np.random.RandomState(seed)
-    polys = []
-    for t in range(128):
-        pts = _random_polygon(rng, t, W, H)
-        polys.append((pts * N)[:N] if len(pts) < N else pts[:N])             # N vertices: the polygon walked again
+    polys = _random_instances(rng, W, H, N)
     groups = [int(g) for g in rng.randint(-2, 3, 128) * 1000003]
     flags = [int(f) for f in rng.choice([0, 1, 3, 3], 128)]
     masks, counts = _device_masks(polys, groups, flags, W, H)
@@ -313,6 +238,37 @@ def test_masks_equal_the_transcription_on_random_polygons(W, H, N, seed):
     bad = [k for k in range(128) if not np.array_equal(masks[k], want[k])]
     assert not bad, "instances %r differ" % bad[:8]
     assert counts.tolist() == (want > 0).sum((1, 2)).tolist()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,H,N,seed", [(97, 61, 16, 0), (33, 130, 64, 2), (2, 3, 3, 3)])
+def test_wave_and_workgroup_scan_lines_agree(W, H, N, seed):
+    """The two forms of csrc/scanline.h share neither sort nor compaction: the polygons of the test above, each alone
+    in its group and drawn, through cp_class_instance_masks (wave form), cp_polygon_masks (workgroup form, stores to
+    memory) and cp_polygon_paint (workgroup form, stores to LDS) against the host F and O, byte for byte.  A width
+    that is no multiple of 16, the wave form's 64 vertices, a canvas smaller than one store."""
+    import torch
+    from centerpoly_amd.datasets import ground_truth
+    polys = _random_instances(np.random.RandomState(seed), W, H, N)
+    n = len(polys)
+    FO = [_fill_outline(tuple(pts), W, H) for pts in polys]
+    want = np.stack([((F & ~O) * 255).astype(np.uint8) for F, O in FO])
+    wave, wave_counts = _device_masks(polys, list(range(n)), [1] * n, W, H)
+    L = _C.lib()
+    xy = torch.tensor(polys, dtype=torch.int32).reshape(n * N, 2).cuda()
+    first = (ctypes.c_int32 * (n + 1))(*range(0, n * N + 1, N))
+    group = torch.full((n, H, W), 77, dtype=torch.uint8, device="cuda")
+    counts = torch.full((n,), -5, dtype=torch.int32, device="cuda")
+    nbytes = L.cp_polygon_masks_workspace_bytes(n, n * N)
+    ws = _C.workspace(nbytes, "cuda")
+    _C.check(L.cp_polygon_masks(_C.ptr(xy), first, n, H, W, _C.ptr(group), _C.ptr(counts), _C.ptr(ws), nbytes,
+                                _C.stream()), "cp_polygon_masks")
+    group = group.cpu().numpy()
+    assert np.array_equal(wave, want) and np.array_equal(group, want) and np.array_equal(wave, group)
+    assert wave_counts.tolist() == counts.cpu().numpy().tolist() == (want > 0).sum((1, 2)).tolist()
+    painted = torch.stack([ground_truth.paint([np.array(pts, np.int32)], [255], 0, (W, H), "cuda") for pts in polys])
+    bad = [k for k in range(n) if not np.array_equal(painted[k].cpu().numpy(), FO[k][0] * 255)]
+    assert not bad, "painted polygons %r differ from the host fill" % bad[:8]
 
 
 def _host_selection(z, ds):
