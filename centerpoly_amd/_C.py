@@ -16,7 +16,7 @@ CP_OK = 0
 REP = {"cartesian": 0, "polar": 1, "polar_fixed": 2}
 HEATMAP_UMICH, HEATMAP_ELLIPSE = 0, 1           # CP_HEATMAP_* of cp_polydet_targets_ex
 L1_PLAIN, L1_POLAR, L1_POLAR_FIXED, L1_RELU20, L1_SMOOTH = 0, 1, 2, 3, 4
-DCN_BWD_EXACT_F32, DCN_BWD_NARROW_TILES, DCN_BWD_ROUND1_KERNELS = 1, 2, 4
+DCN_BWD_EXACT_F32, DCN_BWD_NARROW_TILES = 1, 2
 DCN_CONTRACTION = {"f32": 0, "bf16x3": 1, "bf16x3_region": 3}     # (+1 = "..._PREPARED": weights already in the workspace)
 
 

@@ -44,6 +44,7 @@
 // Small-spatial layers split the input channels over workgroups (grid z); their partial
 // grad_offset / grad_mask sums meet in a reduce kernel.
 #include "cp_common.h"
+#include "dcn_internal.h"
 
 #include <stdlib.h>
 #include <type_traits>

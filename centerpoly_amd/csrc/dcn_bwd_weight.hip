@@ -22,6 +22,7 @@
 #include <stdlib.h>
 
 #include "cp_common.h"
+#include "dcn_internal.h"
 
 namespace {
 

@@ -611,10 +611,6 @@ int launch_bf16x3(const DcnFwdArgs& a, const void* wp, hipStream_t st) {
   return cp_launch_status();
 }
 
-int out_extent(int in, int pad, int dil, int stride) {
-  return (in + 2 * pad - (dil * 2 + 1)) / stride + 1;
-}
-
 }  // namespace
 
 extern "C" size_t cp_dcn_v2_forward_workspace_bytes(const cp_dcn_shape* s) {

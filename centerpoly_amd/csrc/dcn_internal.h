@@ -1,6 +1,11 @@
-// Internal interface between the translation units of the DCNv2 forward (not part of the C ABI).
+// Internal interface between the DCNv2 translation units (not part of the C ABI).
 #pragma once
 #include "cp_common.h"
+
+// output extent of the 3x3 kernel along one axis
+static inline int out_extent(int in, int pad, int dil, int stride) {
+  return (in + 2 * pad - (dil * 2 + 1)) / stride + 1;
+}
 
 // region-sampling split-bf16 kernel (dcn_fwd_region.hip): 3x3, stride 1, pad 1, dilation 1, Cin % 16 == 0
 bool cp_dcn_region_supported(const cp_dcn_shape* s);
@@ -18,3 +23,18 @@ int cp_dcn_region_forward(const cp_dcn_shape* s, const float* x, const float* of
                           const float* bias, const float* ep_scale, const float* ep_shift, int32_t relu, float* out,
                           const void* om_wp, const float* om_bias, float* om_out, float* partial, int ksplit,
                           hipStream_t st);
+
+// dcn_bwd_data.hip: the register-resident grad-column kernel for the data gradients
+bool cp_dcn_bwd_data2_supported(const cp_dcn_shape* s);
+size_t cp_dcn_bwd_data2_workspace_bytes(const cp_dcn_shape* s);
+int cp_dcn_bwd_data2(const cp_dcn_shape* s, const float* x, const float* offset, int64_t offset_bstride,
+                     const float* mask, int64_t mask_bstride, int32_t mask_is_logit, const float* weight,
+                     const float* grad_out, float* grad_x, float* grad_offset, int64_t grad_offset_bstride,
+                     float* grad_mask, int64_t grad_mask_bstride, int32_t flags, void* workspace, size_t workspace_bytes,
+                     hipStream_t st);
+
+// dcn_bwd_weight.hip: the weight gradient with columns sampled straight into the MFMA operand
+bool cp_dcn_bwd_weight2_supported(const cp_dcn_shape* s);
+int cp_dcn_bwd_weight2(const cp_dcn_shape* s, const float* x, const float* offset, int64_t offset_bstride,
+                       const float* mask, int64_t mask_bstride, int32_t mask_is_logit, const float* grad_out,
+                       float* grad_weight, float* grad_bias, int32_t flags, hipStream_t st);

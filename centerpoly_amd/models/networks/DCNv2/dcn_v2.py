@@ -122,50 +122,15 @@ class _DCNv2Function(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         x, om, weight = ctx.saved_tensors
-        stride, pad, dil, dg = ctx.cfg
-        L = _C.lib()
-        s = _shape(x, weight, stride, pad, dil, dg)
-        K = s.kh * s.kw
-        Ho, Wo = om.shape[2], om.shape[3]
-        grad_out = grad_out.contiguous()
-        gx = torch.empty_like(x)                         # (overwritten: the library zero-fills it itself)
-        gom = torch.empty_like(om)
-        gw = _C.zeros(weight.shape, weight.device)
-        gb = _C.zeros((s.Cout,), x.device)
-        bs = 3 * K * Ho * Wo
-        off_m = 4 * 2 * K * Ho * Wo
-        ws = _C.workspace(L.cp_dcn_v2_backward_workspace_bytes(s), x.device)
-        gmask_ptr = _C.c_void_p(gom.data_ptr() + off_m)
-
-        def call(data, wgt, bias_):
-            rc = L.cp_dcn_v2_backward(s, _C.ptr(x), _C.ptr(om), bs, _C.c_void_p(om.data_ptr() + off_m),
-                                      bs, 1, _C.ptr(weight), _C.ptr(grad_out),
-                                      _C.ptr(gx) if data else None, _C.ptr(gom) if data else None, bs,
-                                      gmask_ptr if data else None, bs, _C.ptr(gw) if wgt else None,
-                                      _C.ptr(gb) if bias_ else None, DCN.backward_flags, _C.ptr(ws), ws.numel(),
-                                      _C.stream())
-            _C.check(rc, "cp_dcn_v2_backward")
-
-        timer = _C.kernel_timer
-        if timer is None:
-            call(True, True, True)
-        else:
-            # bench.py's roofline_bwd: the same entry point called once per gradient group so the
-            # data and weight kernels get their own HIP-event brackets (same kernels, same inputs)
-            key = (s.Cin, s.Cout, Ho, Wo, s.B)
-            for tag, sel in (("dcn_bwd_data", (True, False, False)), ("dcn_bwd_weight", (False, True, False)),
-                             ("dcn_bwd_bias", (False, False, True))):
-                end = timer.start((tag,) + key)
-                call(*sel)
-                end.record()
-        return gx, gom, gw, (gb if ctx.has_bias else None), None, None, None, None
+        return _dcn_backward(x, om, weight, grad_out, ctx.has_bias, ctx.cfg) + (None, None, None, None)
 
 
-def _dcn_backward(x, om, weight, grad_out, has_bias):
-    """cp_dcn_v2_backward on the raw 27-channel tensor: (grad_x, grad_om, grad_weight, grad_bias)."""
+def _dcn_backward(x, om, weight, grad_out, has_bias, cfg=(1, 1, 1, 1)):
+    """cp_dcn_v2_backward on the raw 27-channel tensor: (grad_x, grad_om, grad_weight, grad_bias).
+    `cfg` = (stride, pad, dil, deformable_groups)."""
     L = _C.lib()
-    s = _shape(x, weight, 1, 1, 1, 1)
-    K = 9
+    s = _shape(x, weight, *cfg)
+    K = s.kh * s.kw
     Ho, Wo = om.shape[2], om.shape[3]
     grad_out = grad_out.contiguous()
     gx = torch.empty_like(x)                             # (overwritten: the library zero-fills it itself)
@@ -175,12 +140,13 @@ def _dcn_backward(x, om, weight, grad_out, has_bias):
     bs = 3 * K * Ho * Wo
     off_m = 4 * 2 * K * Ho * Wo
     ws = _C.workspace(L.cp_dcn_v2_backward_workspace_bytes(s), x.device)
+    gmask_ptr = _C.c_void_p(gom.data_ptr() + off_m)
 
     def call(data, wgt, bias_):
         rc = L.cp_dcn_v2_backward(s, _C.ptr(x), _C.ptr(om), bs, _C.c_void_p(om.data_ptr() + off_m),
                                   bs, 1, _C.ptr(weight), _C.ptr(grad_out),
                                   _C.ptr(gx) if data else None, _C.ptr(gom) if data else None, bs,
-                                  _C.c_void_p(gom.data_ptr() + off_m) if data else None, bs, _C.ptr(gw) if wgt else None,
+                                  gmask_ptr if data else None, bs, _C.ptr(gw) if wgt else None,
                                   _C.ptr(gb) if bias_ else None, DCN.backward_flags, _C.ptr(ws), ws.numel(),
                                   _C.stream())
         _C.check(rc, "cp_dcn_v2_backward")
@@ -189,6 +155,8 @@ def _dcn_backward(x, om, weight, grad_out, has_bias):
     if timer is None:
         call(True, True, True)
     else:
+        # bench.py's roofline_bwd: the same entry point called once per gradient group so the
+        # data and weight kernels get their own HIP-event brackets (same kernels, same inputs)
         key = (s.Cin, s.Cout, Ho, Wo, s.B)
         for tag, sel in (("dcn_bwd_data", (True, False, False)), ("dcn_bwd_weight", (False, True, False)),
                          ("dcn_bwd_bias", (False, False, True))):

@@ -156,8 +156,7 @@ int cp_dcn_v2_forward_fused(const cp_dcn_shape* s, const float* x, const float* 
  * logits).  flags: 0 = the default kernels (split-bf16 x3 contraction, fp32 accumulate), or a bit-or of CP_DCN_BWD_*. */
 enum {
   CP_DCN_BWD_EXACT_F32 = 1,     /* contract on the exact-fp32 MFMA chain instead of split-bf16 x3                 */
-  CP_DCN_BWD_NARROW_TILES = 2,  /* data gradients: 8-row tiles on every layer (A/B timing of the 12-row form)    */
-  CP_DCN_BWD_ROUND1_KERNELS = 4 /* the first-generation kernels (global float atomics; A/B timing and fallback)  */
+  CP_DCN_BWD_NARROW_TILES = 2   /* data gradients: 8-row tiles on every layer (A/B timing of the 12-row form)    */
 };
 size_t cp_dcn_v2_backward_workspace_bytes(const cp_dcn_shape* s);
 int cp_dcn_v2_backward(const cp_dcn_shape* s, const float* x, const float* offset,

@@ -604,34 +604,64 @@ def test_dcn_fused_bn_relu_epilogue():
 
 
 DCN_BWD_SHAPES = [(1, 16, 24, 12, 20), (2, 8, 140, 9, 11), (1, 64, 64, 16, 32), (1, 130, 32, 8, 8),
-                  # whole 64-pixel row tiles, all three Cout tiles of the LDS-region kernels
+                  # cp_dcn_bwd_data2 on channel-split plans (maps this small split Cin over grid z and reduce the partial
+                  # grad_offset / grad_mask sums) at Cout <= 64, <= 128 and <= 256: one, two and four weight fragments
                   (1, 16, 24, 6, 64), (2, 10, 70, 5, 128), (1, 6, 200, 4, 64), (1, 64, 64, 9, 192),
-                  # partial last tile per row (KITTI-shaped widths 160 / 80, and 64 + 1)
+                  # partial tiles: heights that are no multiple of the 8-row tile, KITTI-shaped widths 160 / 80, and a
+                  # width of 64 + 1 whose last 16-pixel tile holds one column
                   (1, 16, 16, 6, 160), (2, 8, 24, 5, 80), (1, 12, 8, 3, 65),
-                  # Cout > 256 -> generic kernels
+                  # Cout 260 > 256: data gradients from the generic dcn_bwd_data_kernel (weight from cp_dcn_bwd_weight2)
                   (1, 8, 260, 4, 16)]
+
+
+def _check_dcn_backward_vs_oracle(x, om, w, b, gout, stride=1, pad=1, dil=1):
+    """All five gradients of `_DCNv2Function` (x, offsets + mask logits `om`, weight, bias) against torch autograd
+    through the oracle's DCN at the same stride / pad / dilation."""
+    from centerpoly_amd.models.networks.DCNv2.dcn_v2 import _DCNv2Function
+    tx, tom, tw, tb = (T(v).requires_grad_(True) for v in (x, om, w, b))
+    o1, o2, m = torch.chunk(tom, 3, dim=1)
+    ref = odcn.dcn_v2_forward(tx, torch.cat((o1, o2), 1), torch.sigmoid(m), tw, tb, stride, pad, dil)
+    assert ref.shape == gout.shape
+    ref.backward(T(gout))
+    dx, dom, dw, db = (g(v).requires_grad_(True) for v in (x, om, w, b))
+    out = _DCNv2Function.apply(dx, dom, dw, db, stride, pad, dil, 1)
+    out.backward(g(gout))
+    for name, got, want in (("x", dx.grad, tx.grad), ("om", dom.grad, tom.grad),
+                            ("w", dw.grad, tw.grad), ("b", db.grad, tb.grad)):
+        assert got.shape == want.shape, name
+        scale = want.abs().max().item()
+        np.testing.assert_allclose(got.cpu().numpy(), want.numpy(), rtol=1e-3, atol=2e-5 * scale,
+                                   err_msg="grad_" + name)
 
 
 @pytest.mark.parametrize("shape", DCN_BWD_SHAPES, ids=lambda s: "x".join(map(str, s)))
 def test_dcn_backward_vs_oracle_autograd(shape):
     """grad_input, grad_offset, grad_mask(logit), grad_weight, grad_bias vs torch autograd
     through the oracle's DCN (the `DCN` module path: conv_offset_mask output `om` is a leaf)."""
-    from centerpoly_amd.models.networks.DCNv2.dcn_v2 import _DCNv2Function
     B, Cin, Cout, H, W = shape
     x, om, w, b = _dcn_inputs("bwd%dx%d" % (Cin, Cout), *shape)
     gout = synth.normal("dcn/bwd/go%dx%d" % (Cin, Cout), (B, Cout, H, W))
-    tx, tom, tw, tb = (T(v).requires_grad_(True) for v in (x, om, w, b))
-    o1, o2, m = torch.chunk(tom, 3, dim=1)
-    ref = odcn.dcn_v2_forward(tx, torch.cat((o1, o2), 1), torch.sigmoid(m), tw, tb)
-    ref.backward(T(gout))
-    dx, dom, dw, db = (g(v).requires_grad_(True) for v in (x, om, w, b))
-    out = _DCNv2Function.apply(dx, dom, dw, db, 1, 1, 1, 1)
-    out.backward(g(gout))
-    for name, got, want in (("x", dx.grad, tx.grad), ("om", dom.grad, tom.grad),
-                            ("w", dw.grad, tw.grad), ("b", db.grad, tb.grad)):
-        scale = want.abs().max().item()
-        np.testing.assert_allclose(got.cpu().numpy(), want.numpy(), rtol=1e-3, atol=2e-5 * scale,
-                                   err_msg="grad_" + name)
+    _check_dcn_backward_vs_oracle(x, om, w, b, gout)
+
+
+# Inputs that only the generic pair (dcn_bwd_data_kernel / dcn_bwd_weight_kernel) serves: (B, Cin, Cout, H, W, stride, pad, dil)
+DCN_BWD_FALLBACK_CASES = [(1, 8, 12, 9, 11, 2, 1, 1),      # stride 2, output 5 x 6
+                          (2, 6, 140, 7, 10, 1, 0, 1),     # pad != dil, output 5 x 8, a ragged second 128-channel slab
+                          (1, 4, 6, 9, 12, 2, 2, 2),       # stride 2 with dilation 2, output 5 x 6
+                          (1, 5, 9, 5, 131, 2, 1, 1)]      # output rows of 66 pixels: the 64-pixel tiles straddle rows
+
+
+@pytest.mark.parametrize("case", DCN_BWD_FALLBACK_CASES, ids=lambda c: "x".join(map(str, c)))
+def test_dcn_backward_fallback_kernels_vs_oracle_autograd(case):
+    """The same comparison on strided, dilated and pad != dilation inputs (outside every network configuration): both
+    generic kernels on their own inputs, `om` and grad_out at the output size [B, 27 | Cout, Ho, Wo]."""
+    B, Cin, Cout, H, W, stride, pad, dil = case
+    Ho, Wo = (H + 2 * pad - 2 * dil - 1) // stride + 1, (W + 2 * pad - 2 * dil - 1) // stride + 1
+    tag = "fb%dx%ds%dp%dd%d" % (Cin, Cout, stride, pad, dil)
+    x, _, w, b = _dcn_inputs(tag, B, Cin, Cout, H, W)
+    om = synth.normal("dcn/%s/om_out" % tag, (B, 27, Ho, Wo), 0.0, 2.0)
+    gout = synth.normal("dcn/%s/go" % tag, (B, Cout, Ho, Wo))
+    _check_dcn_backward_vs_oracle(x, om, w, b, gout, stride, pad, dil)
 
 
 @pytest.mark.parametrize("shape", [(2, 64, 64, 64, 128), (1, 128, 64, 128, 128)], ids=["64->64 fused forward", "128->64 separate conv"])
@@ -717,11 +747,13 @@ def test_dcn_backward_overwrites_grad_x_and_flags(scale):
         else:                                            # cold path: float atomics, summation order varies
             np.testing.assert_allclose(gx.numpy(), base_x.numpy(), rtol=0, atol=1e-5 * sx, err_msg="fill %r" % fill)
             assert torch.equal(gom, base_om), fill
-    for flags in (_C.DCN_BWD_EXACT_F32, _C.DCN_BWD_NARROW_TILES, _C.DCN_BWD_ROUND1_KERNELS):
+    for flags in (_C.DCN_BWD_EXACT_F32, _C.DCN_BWD_NARROW_TILES):
         gx, gom = run(flags, float("nan"))
         np.testing.assert_allclose(gx.numpy(), base_x.numpy(), rtol=0, atol=2e-4 * sx, err_msg="flags %d" % flags)
-    assert L.cp_dcn_v2_backward(s, _C.ptr(xg), _C.ptr(omg), bs, _C.c_void_p(omg.data_ptr() + off_m), bs, 1, _C.ptr(wg),
-                                _C.ptr(gog), None, None, bs, None, bs, None, None, 64, _C.ptr(ws), nws, _C.stream()) == -1
+    for unknown in (64, 4):                              # no such flag: CP_EINVAL
+        assert L.cp_dcn_v2_backward(s, _C.ptr(xg), _C.ptr(omg), bs, _C.c_void_p(omg.data_ptr() + off_m), bs, 1, _C.ptr(wg),
+                                    _C.ptr(gog), None, None, bs, None, bs, None, None, unknown, _C.ptr(ws), nws,
+                                    _C.stream()) == -1, unknown
 
 
 def test_dcn_backward_propagates_non_finite_grad_out():

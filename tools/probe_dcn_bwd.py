@@ -7,7 +7,7 @@ from centerpoly_amd import _C, synth
 
 L = _C.lib()
 dev = "cuda"
-FLAGS = int(os.environ.get("PROBE_BWD_FLAGS", "0"))      # bit-or of _C.DCN_BWD_* (1 exact f32, 2 narrow tiles, 4 round-1 kernels)
+FLAGS = int(os.environ.get("PROBE_BWD_FLAGS", "0"))      # bit-or of _C.DCN_BWD_* (1 exact f32, 2 narrow tiles)
 
 
 def run(B, ci, co, H, W, what, n=20, off_scale=float(os.environ.get("PROBE_OFF_STD", "0.5"))):
