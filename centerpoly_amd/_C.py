@@ -146,6 +146,9 @@ _SIGNATURES = {
     "cp_maxpool2x2_backward": (c_int32, [_P, _P, _P] + [c_int32] * 4 + [_P]),
     "cp_conv1x1_act_forward": (c_int32, [_P, c_int64, _P, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, c_int64, _P]),
     "cp_soft_nms": (c_int32, [_P, c_int32, c_int32, c_float, c_float, c_float, c_int32]),
+    "cp_soft_nms_device": (c_int32, [_P, c_int32, _P, _P, c_int32, c_float, c_float, c_float, c_int32, _P, _P]),
+    "cp_merge_detections_workspace_bytes": (c_size_t, [c_int32] * 4),
+    "cp_merge_detections": (c_int32, [_P] + [c_int32] * 6 + [c_float] * 3 + [c_int32, _P, _P, _P, c_size_t, _P]),
     "cp_polydet_decode_workspace_bytes": (c_size_t, [c_int32] * 5),
     "cp_polydet_decode": (c_int32, [_P, _P, _P, _P] + [c_int32] * 7 + [_P, _P, _P, _P, c_size_t, _P]),
     "cp_polydet_decode_ex": (c_int32, [_P, _P, _P, _P] + [c_int32] * 8 + [_P, _P, _P, _P, c_size_t, _P]),

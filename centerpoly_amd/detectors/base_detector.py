@@ -119,6 +119,10 @@ class BaseDetector(object):
     def merge_outputs(self, detections):
         raise NotImplementedError
 
+    def merge(self, detections):
+        """What run() makes its `results` with: merge_outputs, unless a detector kept its detections on the device."""
+        return self.merge_outputs(detections)
+
     def debug(self, debugger, images, dets, output, scale=1):
         raise NotImplementedError
 
@@ -187,7 +191,7 @@ class BaseDetector(object):
             post_time += post_process_time - decode_time
             detections.append(dets)
 
-        results = self.merge_outputs(detections)
+        results = self.merge(detections)
         end_time = time.time()
         merge_time += end_time - post_process_time
         ret = {"results": results, "tot": end_time - start_time, "load": load_time,

@@ -52,7 +52,7 @@ extern "C" {
                               cp_conv_mfma_forward_split, cp_activation_split / _unsplit, cp_dla_base_pair_*; no signature changed.
                               Added since, backward compatible (no version change): cp_polydet_targets_ex,
                               cp_class_instance_masks, cp_class_writer_instances, cp_render_overlay_workspace_bytes,
-                              cp_render_overlay, cp_render_heatmap */
+                              cp_render_overlay, cp_render_heatmap, cp_soft_nms_device, cp_merge_detections(_workspace_bytes) */
 
 enum {
   CP_OK = 0,
@@ -694,6 +694,45 @@ int cp_sample_inputs_batch(const uint8_t* images, const int64_t* image_offset, c
  * 2 gaussian.  Only columns 0-4 move; returns the live row count N (>= 0) or CP_EINVAL. */
 int cp_soft_nms(float* boxes_host, int32_t n, int32_t row_stride, float sigma, float Nt,
                 float threshold, int32_t method);
+
+/* cp_soft_nms_device: cp_soft_nms on DEVICE rows, n_seg independent problems in one call (csrc/merge_nms.hip).
+ *   rows       DEVICE fp32, rows of row_stride floats (x1,y1,x2,y2,score,...); only columns 0-4 are read and written
+ *   seg_start, seg_len   DEVICE int32 [n_seg]: segment s is rows [seg_start[s], seg_start[s] + seg_len[s])
+ *   live_out   DEVICE int32 [n_seg]: what cp_soft_nms returns for the segment
+ * Every segment equals, bit for bit, cp_soft_nms on a host copy of it -- the slots at and above the live count
+ * included: a row that fills a hole decays at its new position, so the stale copy it leaves at the end of the live
+ * range keeps its UNDECAYED score (only a row discarded in the last live slot keeps the decayed one).  The double exp
+ * of method 2 is the device library's; its result is rounded to float.  A segment of length 0 (or below) leaves nothing
+ * written but live_out[s] = 0; the segments must not overlap.  One launch, one 64-lane wave per segment.
+ * row_stride >= 5 and n_seg <= 64, otherwise CP_EUNSUPPORTED; null pointers, a negative n_seg or row_stride, a method
+ * outside 0..2: CP_EINVAL; all checks come before any device work.  seg_len <= 4096: the lengths lie on the device, so
+ * the call cannot refuse a longer one -- such a segment is left untouched and reported as live_out[s] = -1.
+ *
+ * cp_merge_detections: PolydetDetector.merge_outputs (src/lib/detectors/polydet.py:62-76) with its soft_nms
+ * (external/nms.pyx:77-170) on the DEVICE rows of the S test scales, literal behaviour.
+ *   rows    DEVICE fp32 [S][K][ncols]: what cp_polydet_post_process wrote for each scale (class in column 5)
+ *   out     DEVICE fp32 [S * K][ncols]       counts  DEVICE int32 [1 + num_classes]: the total, then per class
+ * out[0 : counts[0]] holds class 0's rows, then class 1's, ...; each row x1,y1,x2,y2,score,cls,poly...,depth -- the
+ * reference's `results` with the class column put back.  Rows beyond counts[0] are not specified.  Per class the rows
+ * of every scale in scale order, in row order; with nms != 0 soft_nms(sigma, Nt, threshold, method) in place on the
+ * class block, of which only columns 0-4 move (polygon and depth stay in their slots), the live count is ignored and
+ * the stale slots above it stay part of the block (see cp_soft_nms_device); when the blocks hold more than
+ * max_per_image rows, each class keeps, in order, its rows with score >= the (total - max_per_image)-th smallest score
+ * (np.partition; ties are kept, so counts[0] may exceed max_per_image).  A class value that equals no integer of
+ * [0, num_classes) drops its row.  Scores are assumed finite: with a NaN score the call terminates and stays inside
+ * its buffers, but its result is unspecified.
+ * Three launches (two with nms == 0): partition by class, soft-NMS with one wave per class, cut.  No atomics: a call
+ * repeats its bits.  S * K <= 4096, num_classes <= 64, ncols >= 7, otherwise CP_EUNSUPPORTED; null pointers,
+ * non-positive sizes, max_per_image < 1, a method outside 0..2, out == rows, or workspace_bytes below
+ * cp_merge_detections_workspace_bytes(S, K, ncols, num_classes) (the class-sorted rows and the segment table; 0 for an
+ * unsupported shape): CP_EINVAL.  All checks come before any device work. */
+int cp_soft_nms_device(float* rows, int32_t row_stride, const int32_t* seg_start, const int32_t* seg_len,
+                       int32_t n_seg, float sigma, float Nt, float threshold, int32_t method, int32_t* live_out,
+                       void* stream);
+size_t cp_merge_detections_workspace_bytes(int32_t S, int32_t K, int32_t ncols, int32_t num_classes);
+int cp_merge_detections(const float* rows, int32_t S, int32_t K, int32_t ncols, int32_t num_classes,
+                        int32_t max_per_image, int32_t nms, float sigma, float Nt, float threshold, int32_t method,
+                        float* out, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------- training-target construction --
  * The per-object loop of PolydetDataset.__getitem__ (src/lib/datasets/sample/polydet.py:160-405)
