@@ -34,6 +34,7 @@ constexpr int S1_EPT = 16;                       // elements per thread
 constexpr int S1_TILE = S1_THREADS * S1_EPT;     // 4096
 constexpr int S2_THREADS = 1024;
 constexpr int KMAX = 256;
+constexpr int N2MAX = 128;                       // numbers per polygon row: 64 vertices, the limit of the rest of the chain
 constexpr uint32_t OZ = 0x80000000u;             // orderable(+0.0f)
 
 __device__ __forceinline__ uint32_t f2ord(float f) {
@@ -530,13 +531,15 @@ extern "C" int cp_polydet_decode_ex(const float* heat, const float* polys, const
   CP_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && N2 > 0 && (N2 & 1) == 0 && K > 0);
   CP_CHECK_ARG(rep >= CP_REP_CARTESIAN && rep <= CP_REP_POLAR_FIXED);
   const long long total = (long long)C * H * W;
-  if (K > KMAX || total >= (1ll << 31) || B > 65535) return CP_EUNSUPPORTED;
+  if (K > KMAX || N2 > N2MAX || total >= (1ll << 31) || B > 65535) return CP_EUNSUPPORTED;
   CP_CHECK_ARG((long long)K <= total);
   if (workspace_bytes < cp_polydet_decode_workspace_bytes(B, C, H, W, K)) return CP_EWORKSPACE;
   const DecodePlan p = decode_plan(C, H, W, K);
-  size_t row_lds = (size_t)K * N2 * sizeof(float);
-  if (row_lds > 56 * 1024) return CP_EUNSUPPORTED;
+  size_t row_lds = (size_t)K * N2 * sizeof(float);          // <= KMAX * N2MAX * 4 = 128 KB of the CU's 160 KB
   if (row_lds < sizeof(SelectScratch)) row_lds = sizeof(SelectScratch);
+  // (with the kernel's ~7 KB of static LDS, rows over 56 KB pass the 64 KB a launch gets without asking)
+  if (row_lds > 56 * 1024)
+    (void)hipFuncSetAttribute((const void*)rank_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_lds);
   hipStream_t st = (hipStream_t)stream;
   unsigned long long* buf0 = (unsigned long long*)workspace;
   unsigned long long* buf1 = buf0 + (size_t)B * p.n0;

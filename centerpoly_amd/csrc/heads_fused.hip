@@ -6,15 +6,17 @@
 // resolution, 537 MB at 256 x 512) never goes to memory.  (Separate kernels: the 3x3 launch wrote it, 0.47 ms of which
 // ~30 % were the stores, and cp_conv1x1_act_forward read it back, 0.16 ms.)
 //
-// One workgroup = (8 x 32 pixel tile, one head).  For each of the head's HC / 64 output-channel tiles in turn it runs
-// the 3x3 contraction exactly as conv_mfma_kernel<4, 2, 9> (64 channels x 256 pixels in accumulator registers), then
+// One workgroup = (8 x 32 pixel tile, one work item: a head, or a 64-column segment of a head of 65 .. 128 outputs).
+// For each of the head's HC / 64 output-channel tiles in turn it runs the 3x3 contraction exactly as
+// conv_mfma_kernel<4, 2, 9> (64 channels x 256 pixels in accumulator registers), then
 //   * adds the bias, applies ReLU, splits to bf16 halves IN PLACE: the accumulator layout of
 //     v_mfma_f32_16x16x32_bf16 (lane = pixel column, 4 registers = 4 consecutive channel rows) is already a B operand of
 //     the next MFMA -- rows 4g..4g+3 of two 16-row tiles give the 8 k-values of lane group g, with the 1x1 weights
 //     permuted to the same k order by the prologue (no lane movement, no LDS);
 //   * accumulates out2[class][pixel] += W2[class][those 32 channels] * that fragment (2 x 4 x 2 x 3 MFMAs per tile,
 //     +11 % over the 3x3's 432).
-// After the last tile: + bias2, 64-byte row-segment stores of the head's <= 32 (or <= 64) output channels.
+// After the last tile: + bias2, 64-byte row-segment stores of the item's <= 32 (or <= 64) output channels.  (A wide
+// head's 3x3 contraction so runs twice, once per segment; an MT2 = 8 form would hold 192 accumulator registers.)
 #include "cp_common.h"
 
 namespace {
@@ -24,7 +26,7 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int KC = 32, TW = 32, TH = 8, LW = TW + 2, LH = TH + 2, MT = 4, NT = 4, RW = 2;
 constexpr int PLANE = 4 * LH * LW, UNITS = PLANE, ITERS = (UNITS + 255) / 256;
 constexpr unsigned OOB = 0xFFFFFFF0u;
-constexpr int MAXH = 4;
+constexpr int MAXH = 4, MAXI = 2 * MAXH;     // heads; work items (a head of more than 64 outputs is two)
 
 // wp2[((mt2 * KS2 + ks) * 2 + hl) * 64 + lane][j] = half(hl) of W2[c = 16 mt2 + (lane & 15)][co(ks, lane >> 4, j)],
 // ks = 2 cl + p (cl: 64-channel tile of the head, p: pair of 16-row fragments), g = lane >> 4,
@@ -55,11 +57,15 @@ struct HeadsArgs {
   const float* x;
   const bf16x8* wp1;          // cp_conv_mfma_prepare layout of the concatenated 3x3 weights [nheads * HC][Cin][3][3]
   const float* b1;            // [nheads * HC]
-  const bf16x8* wp2[MAXH];
-  const float* b2[MAXH];      // [cout] or null
-  float* out[MAXH];           // [B][cout][H][W]
-  int cout[MAXH];
-  int Cin, H, W, nchunk, nheads, HC, tiles_x;
+  // one work item = up to 64 output channels of a head: a head of 65 .. 128 outputs is two items over the same 3x3
+  // tiles, each with its own permuted 1x1 weights, bias slice and output slice (all other heads: item = head)
+  const bf16x8* wp2[MAXI];
+  const float* b2[MAXI];      // [cout] or null
+  float* out[MAXI];           // the item's first channel of image 0 in the head's [B][cout of the head][H][W]
+  long long ostride[MAXI];    // elements from one image to the next there: (cout of the head) * H * W
+  int cout[MAXI];             // the item's channels, <= 64
+  int head[MAXI];             // its head: 64-channel tiles head * HC / 64 ... of the concatenated 3x3 output
+  int Cin, H, W, nchunk, nitems, HC, tiles_x;
 };
 
 // MT2: 16-class fragments per head (2: up to 32 output channels, 4: up to 64)
@@ -71,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void conv_heads_fused_kernel(HeadsArgs a) {
   // (XCD-aware order, as in conv_mfma.hip: logical neighbours -- the heads of one tile, then the next tile -- share an L2)
   int lw = blockIdx.x;
   if ((gridDim.x & 7) == 0) lw = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  const int head = lw % a.nheads, tile = lw / a.nheads;
+  const int item = lw % a.nitems, tile = lw / a.nitems, head = a.head[item];
   const int x0 = (tile % a.tiles_x) * TW, y0 = (tile / a.tiles_x) * TH, b = blockIdx.y;
   const int HW = a.H * a.W;
   const int ncl = a.HC / 64, KS2 = a.HC / 32;
@@ -90,7 +96,7 @@ __global__ __launch_bounds__(256, 2) void conv_heads_fused_kernel(HeadsArgs a) {
   const unsigned cstep = (unsigned)HW * 4u;
   const long long tstride = (long long)a.nchunk * 9 * 2 * 64;          // fragments per 16-row tile of the 3x3 weights
   const int bbase = (g * LH + wid * RW) * LW + c;
-  const bf16x8* wq2 = a.wp2[head] + lane;
+  const bf16x8* wq2 = a.wp2[item] + lane;
 
   f32x4 acc2[MT2][NT];                                                 // the head's outputs: [16-class fragment][n]
 #pragma unroll
@@ -214,9 +220,9 @@ __global__ __launch_bounds__(256, 2) void conv_heads_fused_kernel(HeadsArgs a) {
   }
 
   // ---- epilogue: D[row = 4 g + r (class)][col = c (pixel)] ----
-  const int co_n = a.cout[head];
-  float* ob = a.out[head] + (long long)b * co_n * HW;
-  const float* b2 = a.b2[head];
+  const int co_n = a.cout[item];
+  float* ob = a.out[item] + (long long)b * a.ostride[item];
+  const float* b2 = a.b2[item];
 #pragma unroll
   for (int m2 = 0; m2 < MT2; ++m2) {
 #pragma unroll
@@ -237,8 +243,8 @@ __global__ __launch_bounds__(256, 2) void conv_heads_fused_kernel(HeadsArgs a) {
 // Input-resident form (Cin <= 96: the whole (8 + 2) x (32 + 2) halo tile of every input channel fits in LDS as bf16
 // hi | lo, 43.5 KB per 32 channels).  The form above re-stages -- loads, splits, stores -- the same input tile for each
 // of a head's HC / 64 channel tiles, and the heads of a pixel tile sit in different workgroups on different XCDs: the
-// PMC passes showed ~1 GB fetched for a 34 MB input.  Here one workgroup = 8 waves = (pixel tile, TWO heads): the tile
-// is staged ONCE by all 512 threads, then waves 0-3 run head 2 i and waves 4-7 head 2 i + 1 over it, each through its
+// PMC passes showed ~1 GB fetched for a 34 MB input.  Here one workgroup = 8 waves = (pixel tile, TWO work items): the
+// tile is staged ONCE by all 512 threads, then waves 0-3 run item 2 i and waves 4-7 item 2 i + 1 over it, each through its
 // channel tiles, with no further barrier (8 waves per CU as before, one staging instead of eight).
 template <int MT2>
 __global__ __launch_bounds__(512, 2) void conv_heads_fused_res_kernel(HeadsArgs a) {
@@ -246,13 +252,13 @@ __global__ __launch_bounds__(512, 2) void conv_heads_fused_res_kernel(HeadsArgs 
 
   const int tid = threadIdx.x, lane = tid & 63, wid = (tid >> 6) & 3, g = lane >> 4, c = lane & 15;
   const int hsel = __builtin_amdgcn_readfirstlane(tid >> 8);
-  const int npair = (a.nheads + 1) / 2;
+  const int npair = (a.nitems + 1) / 2;
   // XCD-aware order: consecutive workgroups go round-robin over the 8 XCDs, so the head pairs of one tile (and the
   // tiles sharing its halo rows) fetched the input through different L2s -- 114 MB on the fabric side for a 34 MB input
   // (PMC FETCH_SIZE).  Workgroup w takes the logical index (w % 8) * (n / 8) + w / 8: logical neighbours share an XCD.
   int lw = blockIdx.x;
   if ((gridDim.x & 7) == 0) lw = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-  const int head = 2 * (lw % npair) + hsel, tile = lw / npair;
+  const int item = 2 * (lw % npair) + hsel, tile = lw / npair;
   const int x0 = (tile % a.tiles_x) * TW, y0 = (tile / a.tiles_x) * TH, b = blockIdx.y;
   const int HW = a.H * a.W;
   const int ncl = a.HC / 64, KS2 = a.HC / 32;
@@ -293,11 +299,12 @@ __global__ __launch_bounds__(512, 2) void conv_heads_fused_res_kernel(HeadsArgs 
     }
   }
   __syncthreads();
-  if (head >= a.nheads) return;                                        // odd number of heads: the last pair's second half
+  if (item >= a.nitems) return;                                        // odd number of items: the last pair's second half
+  const int head = a.head[item];
 
   const long long tstride = (long long)a.nchunk * 9 * 2 * 64;
   const int bbase = (g * LH + wid * RW) * LW + c;
-  const bf16x8* wq2 = a.wp2[head] + lane;
+  const bf16x8* wq2 = a.wp2[item] + lane;
 
   f32x4 acc2[MT2][NT];
 #pragma unroll
@@ -390,9 +397,9 @@ __global__ __launch_bounds__(512, 2) void conv_heads_fused_res_kernel(HeadsArgs 
     }
   }
 
-  const int co_n = a.cout[head];
-  float* ob = a.out[head] + (long long)b * co_n * HW;
-  const float* b2 = a.b2[head];
+  const int co_n = a.cout[item];
+  float* ob = a.out[item] + (long long)b * a.ostride[item];
+  const float* b2 = a.b2[item];
 #pragma unroll
   for (int m2 = 0; m2 < MT2; ++m2) {
 #pragma unroll
@@ -416,7 +423,8 @@ extern "C" {
 // (always four 16-class fragments: zero rows past cout, so that one layout serves both kernel forms)
 size_t cp_heads_fused_w2_bytes(int32_t head_conv) { return (size_t)4 * (head_conv / 32) * 2 * 64 * 16; }
 
-// w2: the head's 1x1 weight [cout][head_conv] (cout <= 64, head_conv a multiple of 64)
+// w2: the head's 1x1 weight [cout][head_conv] (cout <= 64, head_conv a multiple of 64); for a head of 65 .. 128
+// outputs, one call per 64-row segment of w2 into consecutive blocks of cp_heads_fused_w2_bytes (see the header)
 int cp_heads_fused_prepare_w2(const float* w2, int32_t cout, int32_t head_conv, void* w2perm, void* stream) {
   CP_CHECK_ARG(w2 && w2perm && cout >= 1 && cout <= 64 && head_conv >= 64 && head_conv % 64 == 0);
   const int total = 4 * (head_conv / 32) * 2 * 64;
@@ -437,30 +445,38 @@ int cp_heads_fused_forward(const float* x, const void* wperm1, const float* b1, 
   a.x = x;
   a.wp1 = (const bf16x8*)wperm1;
   a.b1 = b1;
-  for (int h = 0; h < MAXH; ++h) {
-    const bool on = h < nheads;
-    if (on) {
-      CP_CHECK_ARG(w2perm[h] && out[h] && cout[h] >= 1);
-      if (cout[h] > 64) return CP_EUNSUPPORTED;
+  for (int h = 0; h < nheads; ++h) {
+    CP_CHECK_ARG(w2perm[h] && out[h] && cout[h] >= 1);
+    if (cout[h] > 128) return CP_EUNSUPPORTED;
+  }
+  const long long HWl = (long long)H * W;
+  int ni = 0, widest = 0;
+  for (int h = 0; h < nheads; ++h)
+    for (int c0 = 0; c0 < cout[h]; c0 += 64) {                         // the head's 64-column segments
+      const int cn = cout[h] - c0 < 64 ? cout[h] - c0 : 64;
+      a.wp2[ni] = (const bf16x8*)((const char*)w2perm[h] + (c0 / 64) * cp_heads_fused_w2_bytes(head_conv));
+      a.b2[ni] = b2[h] ? b2[h] + c0 : nullptr;
+      a.out[ni] = out[h] + c0 * HWl;
+      a.ostride[ni] = cout[h] * HWl;
+      a.cout[ni] = cn;
+      a.head[ni] = h;
+      widest = cn > widest ? cn : widest;
+      ++ni;
     }
-    a.wp2[h] = on ? (const bf16x8*)w2perm[h] : nullptr;
-    a.b2[h] = on ? b2[h] : nullptr;
-    a.out[h] = on ? out[h] : nullptr;
-    a.cout[h] = on ? cout[h] : 0;
+  for (int i = ni; i < MAXI; ++i) {
+    a.wp2[i] = nullptr; a.b2[i] = nullptr; a.out[i] = nullptr; a.ostride[i] = 0; a.cout[i] = 0; a.head[i] = 0;
   }
   a.Cin = Cin;
   a.H = H;
   a.W = W;
   a.nchunk = Cin / KC;
-  a.nheads = nheads;
+  a.nitems = ni;
   a.HC = head_conv;
   a.tiles_x = (W + TW - 1) / TW;
   const int tiles = a.tiles_x * ((H + TH - 1) / TH);
-  int widest = 0;
-  for (int h = 0; h < nheads; ++h) widest = cout[h] > widest ? cout[h] : widest;
   const size_t res_lds = (size_t)a.nchunk * 2 * PLANE * sizeof(bf16x8);          // input-resident form: Cin <= 96
-  if (res_lds <= 160 * 1024 - 1024 && nheads >= 2) {
-    const int npair = (nheads + 1) / 2;
+  if (res_lds <= 160 * 1024 - 1024 && ni >= 2) {
+    const int npair = (ni + 1) / 2;
     if (widest <= 32) {
       (void)hipFuncSetAttribute((const void*)conv_heads_fused_res_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)res_lds);
       hipLaunchKernelGGL(conv_heads_fused_res_kernel<2>, dim3(tiles * npair, B), dim3(512), res_lds, (hipStream_t)stream, a);
@@ -469,9 +485,9 @@ int cp_heads_fused_forward(const float* x, const void* wperm1, const float* b1, 
       hipLaunchKernelGGL(conv_heads_fused_res_kernel<4>, dim3(tiles * npair, B), dim3(512), res_lds, (hipStream_t)stream, a);
     }
   } else if (widest <= 32)
-    hipLaunchKernelGGL(conv_heads_fused_kernel<2>, dim3(tiles * nheads, B), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(conv_heads_fused_kernel<2>, dim3(tiles * ni, B), dim3(256), 0, (hipStream_t)stream, a);
   else
-    hipLaunchKernelGGL(conv_heads_fused_kernel<4>, dim3(tiles * nheads, B), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(conv_heads_fused_kernel<4>, dim3(tiles * ni, B), dim3(256), 0, (hipStream_t)stream, a);
   return cp_launch_status();
 }
 

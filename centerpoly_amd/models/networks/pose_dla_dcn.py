@@ -705,14 +705,15 @@ def heads_fused_infer(owner, stage, feat, w, b, tails, names):
     """All heads of one output stage as ONE kernel (cp_heads_fused_forward): 3x3 convolution + bias + ReLU + 1x1
     convolution + bias, the nheads x head_conv-channel intermediate never leaves the accumulator registers.
     w, b, tails: see cat_heads.  The permuted weights are kept on `owner` per `stage` (prepared.py).
-    None when the shapes are not the kernel's (more than 4 heads, a head wider than 64 outputs, head_conv not a
-    multiple of 64, input channels not a multiple of 32)."""
+    None when the shapes are not the kernel's (more than 4 heads, a head wider than 128 outputs, head_conv not a
+    multiple of 64, input channels not a multiple of 32).  A head of 65 .. 128 outputs (polygons of more than 32
+    vertices) runs as two 64-column segments of the same launch: its prepared 1x1 weights are two blocks."""
     if not HEADS_FUSED or not conv3x3.mfma_enabled():
         return None
     hcs = {t[2] for t in tails}
     B, cin, H, W = feat.shape
     if not (feat.is_cuda and feat.dtype == torch.float32 and len(tails) <= 4 and len(hcs) == 1 and cin % 32 == 0
-            and all(t[3] <= 64 for t in tails)):
+            and all(t[3] <= 128 for t in tails)):
         return None
     hc = hcs.pop()
     if hc % 64 != 0:
@@ -722,11 +723,15 @@ def heads_fused_infer(owner, stage, feat, w, b, tails, names):
     def build():
         wp1 = conv3x3._prepare(w, cin, w.shape[0], False)
         w2p = []
+        seg = L.cp_heads_fused_w2_bytes(hc)
         for (w_t, b2, _, co) in tails:
             w2 = w_t.t().contiguous()                       # [co][hc]
-            buf = torch.empty(L.cp_heads_fused_w2_bytes(hc), dtype=torch.uint8, device=w.device)
-            _C.check(L.cp_heads_fused_prepare_w2(_C.ptr(w2), co, hc, _C.ptr(buf), _C.stream()),
-                     "cp_heads_fused_prepare_w2")
+            nseg = (co + 63) // 64                          # a head of 65 .. 128 outputs: two 64-row segments
+            buf = torch.empty(nseg * seg, dtype=torch.uint8, device=w.device)
+            for s in range(nseg):
+                _C.check(L.cp_heads_fused_prepare_w2(_C.c_void_p(w2.data_ptr() + 4 * 64 * s * hc), min(64, co - 64 * s),
+                                                     hc, _C.c_void_p(buf.data_ptr() + s * seg), _C.stream()),
+                         "cp_heads_fused_prepare_w2")
             w2p.append(buf)
         return wp1, w2p
     (wp1, w2p), _ = prepared(owner, ("heads_fused", stage), (w,) + tuple(t[0] for t in tails), build)
@@ -838,7 +843,7 @@ class DLASeg(nn.Module):
         self._heads_cat = None
         fcs = [getattr(self, h) for h in self.heads]
         if all(isinstance(fc, nn.Sequential) and len(fc) == 3 and fc[2].kernel_size == (1, 1)
-               and fc[2].out_channels <= 32 and fc[0].bias is not None and fc[0].kernel_size == (3, 3) for fc in fcs):
+               and fc[2].out_channels <= 128 and fc[0].bias is not None and fc[0].kernel_size == (3, 3) for fc in fcs):
             self._heads_cat = cat_heads([(fc[0], fc[2]) for fc in fcs])
         return self
 

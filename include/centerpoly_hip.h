@@ -362,7 +362,11 @@ int cp_conv_direct_wgrad(const float* x, const float* go, float* gw, int32_t B, 
  * w1 = the heads' 3x3 weights concatenated along the output channels ([nheads * HC][Cin][3][3]) and prepared by
  * cp_conv_mfma_prepare(taps 9) into wperm1; w2[h] = the head's 1x1 weight [cout[h]][HC] prepared by
  * cp_heads_fused_prepare_w2.  The HC-channel intermediate stays in accumulator registers (split-bf16 x3 on both
- * stages).  nheads <= 4, cout[h] <= 64, HC % 64 == 0, Cin % 32 == 0; otherwise CP_EUNSUPPORTED. */
+ * stages).  nheads <= 4, cout[h] <= 128, HC % 64 == 0, Cin % 32 == 0; otherwise CP_EUNSUPPORTED.
+ * A head of more than 64 outputs runs as two 64-column segments over the same 3x3 tiles: its w2perm[h] holds two
+ * prepared blocks of cp_heads_fused_w2_bytes(HC) bytes back to back, the first from rows 0..63 of w2
+ * (cp_heads_fused_prepare_w2(w2, 64, ...)), the second from the rest (cp_heads_fused_prepare_w2(w2 + 64 * HC,
+ * cout - 64, ..., w2perm + cp_heads_fused_w2_bytes(HC), ...)).  cp_heads_fused_prepare_w2 itself takes cout <= 64. */
 size_t cp_heads_fused_w2_bytes(int32_t head_conv);
 int cp_heads_fused_prepare_w2(const float* w2, int32_t cout, int32_t head_conv, void* w2perm, void* stream);
 int cp_heads_fused_forward(const float* x, const void* wperm1, const float* b1, const void* const* w2perm,
@@ -816,7 +820,10 @@ int cp_bn_act_backward(const float* x, const float* y, const float* grad_y, cons
 
 /* ----------------------------------------------------------------- decode --
  * heat [B,C,H,W] (already activated), polys [B,2N,H,W], depth [B,1,H,W],
- * reg [B,2,H,W] or NULL (then +0.5).  K <= 256.
+ * reg [B,2,H,W] or NULL (then +0.5).  K <= 256 and N2 = 2N <= 128 (64 vertices, the
+ * limit of the writers, mask kernels and renderer), in any combination: the winners'
+ * polygon rows [K][N2] are staged in up to 128 KB of the CU's 160 KB of LDS.  Beyond
+ * either limit, for cp_polydet_decode and cp_polydet_decode_ex alike: CP_EUNSUPPORTED.
  * Outputs: dets [B,K,2N+7] = [x1,y1,x2,y2,score,cls,poly(2N),depth],
  * inds [B,K] int64 (flat y*W+x), clses [B,K] int32 (both may be NULL).
  * Selection order: score descending, ties by (class, flat index) ascending --
