@@ -505,17 +505,28 @@ __global__ __launch_bounds__(256) void dcn_splitk_reduce_kernel(DcnFwdArgs a, lo
   const int HWo = a.Ho * a.Wo;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total;
        i += (long long)gridDim.x * 256) {
-    float v = 0.f;
-    for (int sidx = 0; sidx < a.splitk; ++sidx) v += a.partial[(long long)sidx * total + i];
     const int co = (int)((i % n_per_b) / HWo);
     float sc = 1.f, sh = 0.f;
     if (a.ep_scale) sc = a.ep_scale[co];
     if (a.ep_shift) sh = a.ep_shift[co];
     else if (a.bias) sh = a.bias[co];
-    v = v * sc + sh;
-    if (a.relu) v = fmaxf(v, 0.f);
-    a.out[i] = v;
+    const float* p[1] = {a.partial + i};
+    float v[1];
+    cp_dcn_slices_values<1>(p, total, a.splitk, sc, sh, a.relu, v);
+    a.out[i] = v[0];
   }
+}
+
+// partial[ks][B][Cout][HWo] -> out[B][Cout][HWo] with bias / folded BN / ReLU
+void launch_splitk_reduce(const float* partial, int ks, const float* bias, const float* ep_scale, const float* ep_shift,
+                          int relu, float* out, int B, int Cout, int Ho, int Wo, hipStream_t st) {
+  DcnFwdArgs ra;
+  ra.partial = const_cast<float*>(partial); ra.out = out; ra.bias = bias; ra.ep_scale = ep_scale; ra.ep_shift = ep_shift;
+  ra.relu = relu; ra.B = B; ra.Ho = Ho; ra.Wo = Wo; ra.Cout = Cout; ra.splitk = ks;
+  const long long n_per_b = (long long)Cout * Ho * Wo;
+  long long nb = ((long long)B * n_per_b + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(dcn_splitk_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, st, ra, n_per_b);
 }
 
 struct Plan {
@@ -672,13 +683,8 @@ extern "C" int cp_dcn_v2_forward(const cp_dcn_shape* s, const float* x, const fl
     const int rc = cp_dcn_region_forward(s, x, offset, offset_bstride, mask, mask_bstride, mask_is_logit, workspace, bias,
                                          ep_scale, ep_shift, relu, out, nullptr, nullptr, nullptr, partial, ks, st);
     if (rc != CP_OK || ks <= 1) return rc;
-    DcnFwdArgs ra;                                          // the slices' raw sums -> out, + bias / folded BN / ReLU
-    ra.partial = partial; ra.out = out; ra.bias = bias; ra.ep_scale = ep_scale; ra.ep_shift = ep_shift; ra.relu = relu;
-    ra.B = s->B; ra.Ho = Ho; ra.Wo = Wo; ra.Cout = s->Cout; ra.splitk = ks;
-    const long long n_per_b = (long long)s->Cout * Ho * Wo;
-    long long nb = ((long long)s->B * n_per_b + 255) / 256;
-    if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(dcn_splitk_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, st, ra, n_per_b);
+    // the slices' raw sums -> out, + bias / folded BN / ReLU
+    launch_splitk_reduce(partial, ks, bias, ep_scale, ep_shift, relu, out, s->B, s->Cout, Ho, Wo, st);
     return cp_launch_status();
   }
   if (p.splitk > 1 || bf) {
@@ -713,6 +719,52 @@ extern "C" int cp_dcn_v2_forward(const cp_dcn_shape* s, const float* x, const fl
   }
   if (p.bn == 64) return launch_pipe<64, 3>(a, st);        // interleaved gather kernel, exact f32 MFMA
   return launch_pipe<128, 2>(a, st);
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// The K-split region launch WITHOUT its reduce: the slices stay in the workspace for a consumer that adds them up while
+// it reads them (cp_depthwise_up_forward_slices: IDAUp's `proj` DCN is read by the up-sample alone).
+extern "C" int cp_dcn_v2_forward_slices_count(const cp_dcn_shape* s, int32_t contraction) {
+  if (!s || s->B <= 0 || s->Cin <= 0 || s->H <= 0 || s->W < 2 || s->Cout <= 0) return 0;
+  if (s->kh != 3 || s->kw != 3 || s->deformable_groups != 1 || s->stride <= 0 || s->dil <= 0 || s->pad < 0) return 0;
+  const bool force = contraction == CP_DCN_BF16X3_REGION || contraction == CP_DCN_BF16X3_REGION_PREPARED;
+  if (contraction != CP_DCN_BF16X3 && contraction != CP_DCN_BF16X3_PREPARED && !force) return 0;
+  if (!cp_dcn_region_supported(s) || !(force || region_pays(s))) return 0;
+  if ((long long)s->H * s->W >= (1ll << 31)) return 0;
+  const Plan p = make_plan(s->B, s->Cin, s->Cout, s->H * s->W);
+  if ((long long)s->B * p.splitk > 65535) return 0;         // (cp_dcn_v2_forward refuses the shape)
+  const int ks = region_ksplit(s);
+  return ks > 1 ? ks : 0;
+}
+
+extern "C" int cp_dcn_v2_forward_slices(const cp_dcn_shape* s, const float* x, const float* offset, int64_t offset_bstride,
+                                        const float* mask, int64_t mask_bstride, int32_t mask_is_logit,
+                                        const float* weight, int32_t contraction, void* workspace, size_t workspace_bytes,
+                                        size_t* partial_offset, void* stream) {
+  CP_CHECK_ARG(s && x && offset && mask && weight && partial_offset);
+  const int ks = cp_dcn_v2_forward_slices_count(s, contraction);
+  if (ks <= 1) return CP_EUNSUPPORTED;
+  if (!workspace || workspace_bytes < cp_dcn_v2_forward_workspace_bytes(s)) return CP_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const bool prepared = contraction == CP_DCN_BF16X3_PREPARED || contraction == CP_DCN_BF16X3_REGION_PREPARED;
+  if (!prepared) {
+    const int rc = cp_dcn_region_prepare(s, weight, workspace, st);
+    if (rc != CP_OK) return rc;
+  }
+  const size_t wpb = wperm_bytes(s);
+  *partial_offset = wpb;
+  return cp_dcn_region_forward(s, x, offset, offset_bstride, mask, mask_bstride, mask_is_logit, workspace, nullptr, nullptr,
+                               nullptr, 0, nullptr, nullptr, nullptr, nullptr, (float*)((char*)workspace + wpb), ks, st);
+}
+
+// The reduce of cp_dcn_v2_forward's K split on its own: out[B][C][HW] = act((sum_s partial[s][B][C][HW]) * ep_scale[c] +
+// ep_shift[c]), NULL = scale 1 / shift 0 -- for a caller of cp_dcn_v2_forward_slices that wants the map after all.
+extern "C" int cp_dcn_splitk_reduce(const float* partial, int32_t nslices, const float* ep_scale, const float* ep_shift,
+                                    int32_t relu, float* out, int32_t B, int32_t C, int64_t HW, void* stream) {
+  CP_CHECK_ARG(partial && out && nslices > 0 && B > 0 && C > 0 && HW > 0);
+  if (HW >= (1ll << 31)) return CP_EUNSUPPORTED;
+  launch_splitk_reduce(partial, nslices, nullptr, ep_scale, ep_shift, relu, out, B, C, 1, (int)HW, (hipStream_t)stream);
+  return cp_launch_status();
 }
 
 // --------------------------------------------------------------------------------------------------------------------

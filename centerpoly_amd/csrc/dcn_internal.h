@@ -7,6 +7,47 @@ static inline int out_extent(int in, int pad, int dil, int stride) {
   return (in + 2 * pad - (dil * 2 + 1)) / stride + 1;
 }
 
+// N elements of one channel of a K-split DCN output from its slices: per element the slices' raw sums added to 0 in slice
+// order, then the epilogue act(v * sc + sh).  p[k] = element k in slice 0, stride = elements between two slices.
+// dcn_splitk_reduce_kernel (dcn_fwd.hip) and the up-sample kernels that read the slices themselves (upsample.hip) both
+// go through this one expression, so a map is the same bits whichever of them forms it.  Eight (then four) slices' loads are issued
+// before their adds (a load-wait-add loop costs a full memory latency per slice); the order of the adds is untouched.
+// U slices' loads of N elements issued before their adds, which stay in slice order
+template <int N, int U>
+__device__ __forceinline__ void cp_dcn_slices_block(const float* (&p)[N], long long stride, int sidx, float (&v)[N]) {
+  float t[U][N];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int k = 0; k < N; ++k) t[u][k] = p[k][(long long)(sidx + u) * stride];
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += t[u][k];
+}
+
+template <int N>
+__device__ inline void cp_dcn_slices_values(const float* (&p)[N], long long stride, int nslices, float sc, float sh,
+                                            int relu, float (&v)[N]) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = 0.f;
+  int sidx = 0;
+  for (; sidx + 8 <= nslices; sidx += 8) cp_dcn_slices_block<N, 8>(p, stride, sidx, v);
+  if (sidx + 4 <= nslices) {
+    cp_dcn_slices_block<N, 4>(p, stride, sidx, v);
+    sidx += 4;
+  }
+  for (; sidx < nslices; ++sidx) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += p[k][(long long)sidx * stride];
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    v[k] = v[k] * sc + sh;
+    if (relu) v[k] = fmaxf(v[k], 0.f);
+  }
+}
+
 // region-sampling split-bf16 kernel (dcn_fwd_region.hip): 3x3, stride 1, pad 1, dilation 1, Cin % 16 == 0
 bool cp_dcn_region_supported(const cp_dcn_shape* s);
 size_t cp_dcn_region_wperm_bytes(const cp_dcn_shape* s);

@@ -7,7 +7,10 @@
 // (col2im + batched GEMM + transposes) spends ~100 us per layer on a memory-bound op; this is
 // one streaming pass: each output pixel reads its 2x2 contributing inputs (L1/L2 resident)
 // and the skip map, float4 stores along x.  HBM-bound: 4*(C*H*W + 2*C*f*f*H*W) bytes.
+// f = 2 and f = 4 run patch kernels (dw_up2_kernel, dw_up4_kernel); both also exist in a form whose input is still the
+// K-split slices of the DCN in front of it (dw_up_slices_kernel, cp_depthwise_up_forward_slices).
 #include "cp_common.h"
+#include "dcn_internal.h"   // cp_dcn_slices_values: the K-split reduce's expression
 
 namespace {
 
@@ -62,6 +65,80 @@ __global__ __launch_bounds__(256) void dw_up_kernel(const float* __restrict__ x,
     for (int q = 0; q < 4 && ox0 + q < Wo; ++q) out[o + q] = v[q];
 }
 
+// the R skip rows of a patch (16 bytes each) at offset o of a map whose rows are Wo long; zeros without a skip map
+template <int R>
+__device__ __forceinline__ void load_skip_rows(const float* __restrict__ skip, long long o, int Wo, f32x4 (&sk)[R]) {
+#pragma unroll
+  for (int e = 0; e < R; ++e)
+    sk[e] = skip ? *reinterpret_cast<const f32x4*>(skip + o + (long long)e * Wo) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// The patch's arithmetic and its stores, shared by dw_up2_kernel and the slices form below (one expression tree: the same
+// bits from both).  in = rows i - 1 .. i + 1, columns 2j - 1 .. 2j + 2, zero outside the map; wc = the channel's [ky][kx]
+// (wave-uniform: scalar loads); sk = the patch's two skip rows when has_skip (loaded by the caller, as early as it can);
+// o = offset of out[2i][4j], Wo = 2 W.
+__device__ __forceinline__ void up2_patch_store(const float (&in)[3][4], const float* __restrict__ wc,
+                                                const f32x4 (&sk)[2], bool has_skip, float* __restrict__ out, long long o,
+                                                int Wo) {
+  float wk[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) wk[a][b] = wc[a * 4 + b];
+#pragma unroll
+  for (int e = 0; e < 2; ++e) {                        // output row 2i + e: input rows (hi, ky = 1 - e), (hi - 1, ky = 3 - e)
+    const float* hi = in[1 + e];
+    const float* lo = in[e];
+    const float* wa = wk[1 - e];
+    const float* wb = wk[3 - e];
+    f32x4 v;
+    v[0] = hi[1] * wa[1] + hi[0] * wa[3] + lo[1] * wb[1] + lo[0] * wb[3];
+    v[1] = hi[2] * wa[0] + hi[1] * wa[2] + lo[2] * wb[0] + lo[1] * wb[2];
+    v[2] = hi[2] * wa[1] + hi[1] * wa[3] + lo[2] * wb[1] + lo[1] * wb[3];
+    v[3] = hi[3] * wa[0] + hi[2] * wa[2] + lo[3] * wb[0] + lo[2] * wb[2];
+    if (has_skip) {
+      v[0] += sk[e][0]; v[1] += sk[e][1]; v[2] += sk[e][2]; v[3] += sk[e][3];
+    }
+    *reinterpret_cast<f32x4*>(out + o + (long long)e * Wo) = v;
+  }
+}
+
+// f = 4: the 4 x 4 output patch of input pixel (i, j) from in = rows i - 1 .. i + 1, columns j - 1 .. j + 1 (zero outside
+// the map); wc = the channel's [8][8] taps (wave-uniform: scalar loads); sk = the patch's four skip rows when has_skip;
+// o = offset of out[4i][4j], Wo = 4 W.
+//   out[4i + e][..] : rows (i, ky 2 + e), (i - 1, ky 6 + e) for e < 2;  (i + 1, ky e - 2), (i, ky e + 2) for e >= 2
+// and the same along x.  Per output the four products are added to 0 in dw_up_kernel's order -- (iy0, ix0),
+// (iy0, ix0 - 1), (iy0 - 1, ix0), (iy0 - 1, ix0 - 1), then the skip -- so the values are that kernel's (a tap outside the
+// map adds 0 * w here where the generic form skips it: the same sum for finite weights).
+__device__ __forceinline__ void up4_patch_store(const float (&in)[3][3], const float* __restrict__ wc,
+                                                const f32x4 (&sk)[4], bool has_skip, float* __restrict__ out, long long o,
+                                                int Wo) {
+  float wk[8][8];
+#pragma unroll
+  for (int a = 0; a < 8; ++a)
+#pragma unroll
+    for (int b = 0; b < 8; ++b) wk[a][b] = wc[a * 8 + b];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int rh = e < 2 ? 1 : 2, kyh = e < 2 ? 2 + e : e - 2;    // (iy0, ky0); the other pair: (iy0 - 1, ky0 + 4)
+    f32x4 v;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int ch = q < 2 ? 1 : 2, kxh = q < 2 ? 2 + q : q - 2;
+      float s = 0.f;
+      s += in[rh][ch] * wk[kyh][kxh];
+      s += in[rh][ch - 1] * wk[kyh][kxh + 4];
+      s += in[rh - 1][ch] * wk[kyh + 4][kxh];
+      s += in[rh - 1][ch - 1] * wk[kyh + 4][kxh + 4];
+      v[q] = s;
+    }
+    if (has_skip) {
+      v[0] += sk[e][0]; v[1] += sk[e][1]; v[2] += sk[e][2]; v[3] += sk[e][3];
+    }
+    *reinterpret_cast<f32x4*>(out + o + (long long)e * Wo) = v;
+  }
+}
+
 // f = 2 (every IDAUp / DLAUp level but one): one thread = a 2 x 4 output patch = output rows 2i, 2i + 1, columns
 // 4j .. 4j + 3, from input rows i - 1 .. i + 1 and columns 2j - 1 .. 2j + 2 -- 12 loads (3 float2 + 6 dwords) for 8
 // outputs instead of 32 for 4 in the generic form, no integer division, two 16-byte skip loads and stores per thread.
@@ -78,11 +155,6 @@ __global__ __launch_bounds__(256) void dw_up2_kernel(const float* __restrict__ x
   if (idx >= H * W2) return;
   const int i = idx / W2, j = idx - i * W2;
   const float* wc = w + (long long)(bc % C) * 16;     // [ky][kx], wave-uniform: scalar loads
-  float wk[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) wk[a][b] = wc[a * 4 + b];
   const float* xc = x + (long long)bc * H * W;
   float in[3][4];                                     // rows i - 1, i, i + 1; columns 2j - 1, 2j, 2j + 1, 2j + 2
 #pragma unroll
@@ -97,24 +169,105 @@ __global__ __launch_bounds__(256) void dw_up2_kernel(const float* __restrict__ x
     in[r][2] = rok ? mid[1] : 0.f;
     in[r][3] = rok ? rgt : 0.f;
   }
-  const int Wo = 2 * W;
-  const long long o = ((long long)bc * 2 * H + 2 * i) * Wo + 4 * j;
+  const long long o = ((long long)bc * 2 * H + 2 * i) * (2 * W) + 4 * j;
+  f32x4 sk[2];
+  load_skip_rows<2>(skip, o, 2 * W, sk);
+  up2_patch_store(in, wc, sk, skip != nullptr, out, o, 2 * W);
+}
+
+// f = 4 (the last IDAUp level): one thread = the 4 x 4 output patch of input pixel (i, j) = output rows 4i .. 4i + 3,
+// columns 4j .. 4j + 3, from the 3 x 3 inputs around it (9 loads for 16 outputs; the generic form: 16 for 4, with an
+// integer division per tap and every weight loaded per lane).
+__global__ __launch_bounds__(256) void dw_up4_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                     const float* __restrict__ skip, float* __restrict__ out, int C, int H,
+                                                     int W) {
+  const int bc = blockIdx.y;
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= H * W) return;
+  const int i = idx / W, j = idx - i * W;
+  const float* xc = x + (long long)bc * H * W;
+  float in[3][3];                                     // rows i - 1 .. i + 1, columns j - 1 .. j + 1 (zero outside)
 #pragma unroll
-  for (int e = 0; e < 2; ++e) {                        // output row 2i + e: input rows (hi, ky = 1 - e), (hi - 1, ky = 3 - e)
-    const float* hi = in[1 + e];
-    const float* lo = in[e];
-    const float* wa = wk[1 - e];
-    const float* wb = wk[3 - e];
-    f32x4 v;
-    v[0] = hi[1] * wa[1] + hi[0] * wa[3] + lo[1] * wb[1] + lo[0] * wb[3];
-    v[1] = hi[2] * wa[0] + hi[1] * wa[2] + lo[2] * wb[0] + lo[1] * wb[2];
-    v[2] = hi[2] * wa[1] + hi[1] * wa[3] + lo[2] * wb[1] + lo[1] * wb[3];
-    v[3] = hi[3] * wa[0] + hi[2] * wa[2] + lo[3] * wb[0] + lo[2] * wb[2];
-    if (skip) {
-      const f32x4 sk = *reinterpret_cast<const f32x4*>(skip + o + (long long)e * Wo);
-      v[0] += sk[0]; v[1] += sk[1]; v[2] += sk[2]; v[3] += sk[3];
-    }
-    *reinterpret_cast<f32x4*>(out + o + (long long)e * Wo) = v;
+  for (int r = 0; r < 3; ++r) {
+    const int iy = i - 1 + r;
+    const bool rok = iy >= 0 && iy < H;
+    const float* row = xc + (long long)(rok ? iy : i) * W + j;
+    const float lft = j > 0 ? row[-1] : 0.f, mid = row[0], rgt = j + 1 < W ? row[1] : 0.f;
+    in[r][0] = rok ? lft : 0.f;
+    in[r][1] = rok ? mid : 0.f;
+    in[r][2] = rok ? rgt : 0.f;
+  }
+  const long long o = ((long long)bc * 4 * H + 4 * i) * (4 * W) + 4 * j;
+  f32x4 sk[4];
+  load_skip_rows<4>(skip, o, 4 * W, sk);
+  up4_patch_store(in, w + (long long)(bc % C) * 64, sk, skip != nullptr, out, o, 4 * W);
+}
+
+// ------------------------------------------------------------------------------------- up-sampling from K-split slices
+// The same two patch forms on the input  x = act((sum_s partial[s]) * scale[c] + shift[c])  that a K-split DCN left as
+// slices (cp_dcn_v2_forward_slices): the reduce launch, the map it writes and the read of that map are gone.  A
+// workgroup forms its input tile + 1-pixel halo ONCE in LDS through cp_dcn_slices_values (the reduce kernel's own
+// expression: the same bits) -- (TH + 2)(TW + 2) / (TH TW) = 1.29 (f = 2) / 1.33 (f = 4) reads per slice element,
+// where patches reading the slices directly would issue 12 n / 9 n loads each -- then every thread takes its patch
+// from the tile.  Zeros outside the map, as the patch kernels' own edge handling gives.
+template <int F>
+__global__ __launch_bounds__(256) void dw_up_slices_kernel(const float* __restrict__ partial, int nslices,
+                                                           long long slice_stride, const float* __restrict__ ep_scale,
+                                                           const float* __restrict__ ep_shift, int relu,
+                                                           const float* __restrict__ w, const float* __restrict__ skip,
+                                                           float* __restrict__ out, int C, int H, int W, int tiles_x) {
+  constexpr int PW = F == 2 ? 2 : 1;                  // input columns per thread
+  constexpr int TH = 8, TW = 32 * PW;                 // input tile: 8 rows x 32 patches
+  __shared__ float tile[TH + 2][TW + 2];
+  const int bc = blockIdx.y, c = bc % C;
+  const int ty = blockIdx.x / tiles_x;
+  const int y0 = ty * TH, x0 = (blockIdx.x - ty * tiles_x) * TW;
+  const float sc = ep_scale ? ep_scale[c] : 1.f, sh = ep_shift ? ep_shift[c] : 0.f;
+  const float* pc = partial + (long long)bc * H * W;
+  // the patch's skip rows first: their loads are under way while the tile is formed, not behind the barrier
+  const int li = threadIdx.x >> 5, lj = (threadIdx.x & 31) * PW;
+  const int i = y0 + li, jx = x0 + lj;                // this thread's input row and first input column
+  const bool live = i < H && jx < W;
+  const int Wo = F * W;
+  const long long o = ((long long)bc * F * H + F * i) * Wo + F * jx;
+  f32x4 sk[F];
+  load_skip_rows<F>(live ? skip : nullptr, o, Wo, sk);
+  // a thread's NE tile elements go through the slices together (branch-free: addresses clamped into the map, the
+  // values outside it dropped afterwards), so up to 8 NE loads are in flight per thread
+  constexpr int TOTAL = (TH + 2) * (TW + 2), NE = (TOTAL + 255) / 256;
+  const float* p[NE];
+  bool inside[NE];
+  int slot[NE];
+#pragma unroll
+  for (int k = 0; k < NE; ++k) {
+    const int e = min((int)threadIdx.x + 256 * k, TOTAL - 1);
+    const int r = e / (TW + 2), q = e - r * (TW + 2);
+    const int iy = y0 - 1 + r, ix = x0 - 1 + q;
+    inside[k] = iy >= 0 && iy < H && ix >= 0 && ix < W;
+    slot[k] = (int)threadIdx.x + 256 * k < TOTAL ? e : -1;
+    p[k] = pc + (long long)min(max(iy, 0), H - 1) * W + min(max(ix, 0), W - 1);
+  }
+  float v[NE];
+  cp_dcn_slices_values<NE>(p, slice_stride, nslices, sc, sh, relu, v);
+#pragma unroll
+  for (int k = 0; k < NE; ++k)
+    if (slot[k] >= 0) (&tile[0][0])[slot[k]] = inside[k] ? v[k] : 0.f;
+  __syncthreads();
+  if (!live) return;
+  if constexpr (F == 2) {
+    float in[3][4];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) in[r][k] = tile[li + r][lj + k];
+    up2_patch_store(in, w + (long long)c * 16, sk, skip != nullptr, out, o, Wo);
+  } else {
+    float in[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) in[r][k] = tile[li + r][lj + k];
+    up4_patch_store(in, w + (long long)c * 64, sk, skip != nullptr, out, o, Wo);
   }
 }
 
@@ -133,8 +286,33 @@ extern "C" int cp_depthwise_up_forward(const float* x, const float* weight, cons
     const dim3 g2((unsigned)(((long long)H * (W / 2) + 255) / 256), B * C);
     hipLaunchKernelGGL(dw_up2_kernel, g2, dim3(256), 0, st, x, weight, skip, out, C, H, W);
   } else if (f == 2) hipLaunchKernelGGL(dw_up_kernel<2>, grid, dim3(256), 0, st, x, weight, skip, out, C, H, W);
-  else if (f == 4) hipLaunchKernelGGL(dw_up_kernel<4>, grid, dim3(256), 0, st, x, weight, skip, out, C, H, W);
+  else if (f == 4 && (long long)H * W < (1ll << 31) - 256) {
+    const dim3 g4((unsigned)(((long long)H * W + 255) / 256), B * C);
+    hipLaunchKernelGGL(dw_up4_kernel, g4, dim3(256), 0, st, x, weight, skip, out, C, H, W);
+  } else if (f == 4) hipLaunchKernelGGL(dw_up_kernel<4>, grid, dim3(256), 0, st, x, weight, skip, out, C, H, W);
   else hipLaunchKernelGGL(dw_up_kernel<8>, grid, dim3(256), 0, st, x, weight, skip, out, C, H, W);
+  return cp_launch_status();
+}
+
+extern "C" int cp_depthwise_up_forward_slices(const float* partial, int32_t nslices, int64_t slice_stride,
+                                              const float* ep_scale, const float* ep_shift, int32_t relu,
+                                              const float* weight, const float* skip, float* out, int32_t B, int32_t C,
+                                              int32_t H, int32_t W, int32_t f, void* stream) {
+  CP_CHECK_ARG(partial && weight && out && nslices > 0 && slice_stride >= 0 && B > 0 && C > 0 && H > 0 && W > 0);
+  if (!((f == 2 && (W & 1) == 0) || f == 4)) return CP_EUNSUPPORTED;   // (the caller keeps reduce + cp_depthwise_up_forward)
+  if ((long long)B * C > 65535) return CP_EUNSUPPORTED;
+  const int tw = f == 2 ? 64 : 32;
+  const int tiles_x = (W + tw - 1) / tw;
+  const long long tiles = (long long)tiles_x * ((H + 7) / 8);
+  if (tiles >= (1ll << 31)) return CP_EUNSUPPORTED;
+  const dim3 grid((unsigned)tiles, B * C);
+  hipStream_t st = (hipStream_t)stream;
+  if (f == 2)
+    hipLaunchKernelGGL(dw_up_slices_kernel<2>, grid, dim3(256), 0, st, partial, nslices, (long long)slice_stride, ep_scale,
+                       ep_shift, relu, weight, skip, out, C, H, W, tiles_x);
+  else
+    hipLaunchKernelGGL(dw_up_slices_kernel<4>, grid, dim3(256), 0, st, partial, nslices, (long long)slice_stride, ep_scale,
+                       ep_shift, relu, weight, skip, out, C, H, W, tiles_x);
   return cp_launch_status();
 }
 

@@ -81,6 +81,49 @@ def dcn_v2_forward_raw(x, om, weight, bias, stride=1, pad=1, dil=1, dg=1, ep_sca
     return out
 
 
+def dcn_v2_slices_count(x, weight, stride=1, pad=1, dil=1, dg=1, contraction="f32"):
+    """Slices the library's K-split region launch leaves for this input (cp_dcn_v2_forward_slices_count): > 1 where
+    dcn_v2_forward_slices applies, else 0."""
+    s = _shape(x, weight, stride, pad, dil, dg)
+    if contraction == "auto":
+        contraction = auto_contraction(s)
+    return _C.lib().cp_dcn_v2_forward_slices_count(s, _C.DCN_CONTRACTION[contraction])
+
+
+def dcn_v2_forward_slices(x, om, weight, stride=1, pad=1, dil=1, dg=1, contraction="f32", owner=None):
+    """dcn_v2_forward_raw without the reduce launch (cp_dcn_v2_forward_slices): the K-split slices' raw sums stay in the
+    workspace.  Returns (ws, byte offset of partial[slice][B][Cout][H][W] in ws, slice count); the caller keeps `ws`
+    until its reader is enqueued on the same stream.  The workspace is the one dcn_v2_forward_raw keeps on `owner`
+    (same slot, same permuted weights): the two routes can alternate on one module."""
+    L = _C.lib()
+    s = _shape(x, weight, stride, pad, dil, dg)
+    Ho, Wo = om.shape[2], om.shape[3]
+    K = s.kh * s.kw
+    bs = 3 * K * Ho * Wo
+    mask_ptr = _C.c_void_p(om.data_ptr() + 4 * 2 * K * Ho * Wo)
+    nws = L.cp_dcn_v2_forward_workspace_bytes(s)
+    if contraction == "auto":
+        contraction = auto_contraction(s)
+    mode = _C.DCN_CONTRACTION[contraction]
+    nsl = L.cp_dcn_v2_forward_slices_count(s, mode)
+    if owner is not None and mode in (1, 3):
+        ws, built = prepared(owner, "dcn_fwd", (weight,), lambda: _C.workspace(nws, x.device),
+                             (mode, tuple(x.shape), tuple(om.shape)))
+        if not built:
+            mode += 1                                    # CP_DCN_BF16X3[_REGION]_PREPARED
+    else:
+        ws = _C.workspace(nws, x.device)
+    off = _C.c_size_t(0)
+    timer = _C.kernel_timer
+    end = timer.start(("dcn_fwd", s.Cin, s.Cout, Ho, Wo, s.B)) if timer is not None else None
+    rc = L.cp_dcn_v2_forward_slices(s, _C.ptr(x), _C.ptr(om), bs, mask_ptr, bs, 1, _C.ptr(weight), mode, _C.ptr(ws), nws,
+                                    _C.ctypes.byref(off), _C.stream())
+    if end is not None:
+        end.record()
+    _C.check(rc, "cp_dcn_v2_forward_slices")
+    return ws, off.value, nsl
+
+
 def dcn_v2_module_forward(x, om_weight, om_bias, weight, bias, ep_scale=None, ep_shift=None, relu=False, owner=None,
                           want_om=False):
     """The whole DCN module in one launch (cp_dcn_v2_forward_fused): conv_offset_mask computed inside the DCN kernel.
@@ -311,3 +354,21 @@ class DCN(nn.Module):
         return dcn_v2_forward_raw(x.contiguous(), om.contiguous(), self.weight, None, self.stride,
                                   self.padding, self.dilation, self.deformable_groups, ep_scale,
                                   ep_shift, relu, getattr(self, "contraction", None) or DCN.infer_contraction, owner=self)
+
+    def forward_slices(self, x):
+        """Inference: forward_fused's offset convolution + DCN launch, stopped before the K-split reduce.  Returns
+        (ws, byte offset, slice count) of dcn_v2_forward_slices -- the caller applies the epilogue while it reads the
+        slices -- or None, with nothing launched, where the library does not split this shape (a split shape never
+        takes the fused module launch, so this is forward_fused's second route)."""
+        if not (x.is_cuda and x.dtype == torch.float32):
+            return None
+        con = getattr(self, "contraction", None) or DCN.infer_contraction
+        x = x.contiguous()
+        cfg = (self.stride, self.padding, self.dilation, self.deformable_groups)
+        if dcn_v2_slices_count(x, self.weight, *cfg, contraction=con) <= 1:
+            return None
+        cm = self.conv_offset_mask
+        om = conv_infer([x], cm, cm.weight, cm.bias, conv=cm)
+        if om is None:
+            om = cm(x)
+        return dcn_v2_forward_slices(x, om.contiguous(), self.weight, *cfg, contraction=con, owner=self)

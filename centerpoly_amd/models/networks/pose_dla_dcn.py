@@ -451,9 +451,20 @@ class Tree(nn.Module):
         self._folded = _fold_conv_bn(self.project[0], self.project[1]) if self.project is not None \
             else None
 
-    def forward(self, x, residual=None, children=None):
+    # inference: a multi-level Tree hands its pooled input down to `tree1`, which would pool the same x with the same
+    # window again (False = both pool, as in training, where the autograd graph keeps its two nodes)
+    share_pool = True
+
+    def _same_pool(self, other):
+        a, b = self.downsample, getattr(other, "downsample", None)
+        return isinstance(other, Tree) and a is not None and b is not None and \
+            (a.kernel_size, a.stride, a.padding, a.dilation, a.ceil_mode) == \
+            (b.kernel_size, b.stride, b.padding, b.dilation, b.ceil_mode)
+
+    def forward(self, x, residual=None, children=None, bottom=None):
         children = [] if children is None else children
-        bottom = x if self.downsample is None else downsample2(self.downsample, x)
+        if bottom is None:                        # (else: the outer tree's pool of this same x)
+            bottom = x if self.downsample is None else downsample2(self.downsample, x)
         if self.project is None:
             residual = bottom
         elif self.project_is_dead:
@@ -470,7 +481,10 @@ class Tree(nn.Module):
             residual = bn_act(self.project[1], conv_train(self.project[0], bottom), relu=False)
         if self.level_root:
             children.append(bottom)
-        x1 = self.tree1(x, residual)
+        if Tree.share_pool and self.levels > 1 and not torch.is_grad_enabled() and self._same_pool(self.tree1):
+            x1 = self.tree1(x, residual, bottom=bottom)
+        else:
+            x1 = self.tree1(x, residual)
         if self.levels == 1:
             return self.root(self.tree2(x1), x1, *children)
         children.append(x1)
@@ -594,6 +608,39 @@ class DeformConv(nn.Module):
             return bn_act(self.actf[0], self.conv(x), relu=True)
         return self.actf(self.conv(x))
 
+    def forward_slices(self, x):
+        """Inference: the DCN stopped before its K-split reduce (DCN.forward_slices) and the folded BatchNorm + ReLU
+        left to the reader of the slices: (ws, byte offset, slice count, scale, shift), or None where the DCN is not
+        split (nothing is launched then)."""
+        r = self.conv.forward_slices(x)
+        if r is None:
+            return None
+        scale, shift = self._folded if getattr(self, "_folded", None) is not None else self.folded_affine()
+        return r + (scale, shift)
+
+
+def depthwise_up_add_slices(proj, x, up, skip):
+    """up(proj(x)) + skip in two launches instead of three where proj's DCN splits its input channels: the up-sample
+    reads the slices itself (cp_depthwise_up_forward_slices) -- no reduce launch, and proj's output map is neither
+    written nor read back.  Bit-identical to depthwise_up_add(proj(x), up, skip).  None, with nothing launched, where
+    the DCN is not split or the up factor does not take the slices kernel (IDAUp.fold_slices_factors)."""
+    f = up.stride[0]
+    B, _, H, W = x.shape
+    C = up.weight.shape[0]
+    if f not in IDAUp.fold_slices_factors or (f == 2 and W % 2) or B * C > 65535:
+        return None
+    r = proj.forward_slices(x)
+    if r is None:
+        return None
+    ws, off, nsl, scale, shift = r
+    out = torch.empty((B, C, H * f, W * f), dtype=torch.float32, device=x.device)
+    skip = skip.contiguous()
+    rc = _C.lib().cp_depthwise_up_forward_slices(_C.c_void_p(ws.data_ptr() + off), nsl, B * C * H * W, _C.ptr(scale),
+                                                 _C.ptr(shift), 1, _C.ptr(up.weight), _C.ptr(skip), _C.ptr(out), B, C, H,
+                                                 W, f, _C.stream())
+    _C.check(rc, "cp_depthwise_up_forward_slices")     # (`ws` is alive up to here: the reader is enqueued)
+    return out
+
 
 def depthwise_up_add(x, up, skip):
     """up(x) + skip in one HIP kernel (inference): `up` is IDAUp's depth-wise ConvTranspose2d."""
@@ -640,6 +687,14 @@ class _DepthwiseUpAdd(torch.autograd.Function):
 
 
 class IDAUp(nn.Module):
+    # inference: where `proj`'s DCN splits its input channels, the up-sample adds the slices up itself
+    # (depthwise_up_add_slices); False = the DCN's reduce launch + depthwise_up_add (tests, A/B runs)
+    fold_slices = True
+    # up factors that take the slices kernel.  The library has one for f = 4 as well, but at the one f = 4 level of
+    # DLA-34 (256 -> 64 @64x128, 8 slices, 64 x 256x512 out) it ran 22.1 us against 7.2 + 11.6 us for the reduce and the
+    # f = 4 patch kernel, so that level keeps its two launches
+    fold_slices_factors = (2,)
+
     def __init__(self, o, channels, up_f):
         super().__init__()
         for i in range(1, len(channels)):
@@ -658,7 +713,9 @@ class IDAUp(nn.Module):
             up, proj = getattr(self, "up_%d" % k), getattr(self, "proj_%d" % k)
             aligned = layers[i].is_cuda and (layers[i].shape[3] * up.stride[0]) % 4 == 0
             if fused and aligned and up.stride[0] in (2, 4, 8):
-                summed = depthwise_up_add(proj(layers[i]), up, layers[i - 1])
+                summed = depthwise_up_add_slices(proj, layers[i], up, layers[i - 1]) if IDAUp.fold_slices else None
+                if summed is None:
+                    summed = depthwise_up_add(proj(layers[i]), up, layers[i - 1])
             elif not fused and aligned and up.stride[0] in (2, 4):
                 summed = _DepthwiseUpAdd.apply(proj(layers[i]), up.weight, layers[i - 1], up.stride[0])
             else:

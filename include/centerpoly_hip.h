@@ -52,7 +52,8 @@ extern "C" {
                               cp_conv_mfma_forward_split, cp_activation_split / _unsplit, cp_dla_base_pair_*; no signature changed.
                               Added since, backward compatible (no version change): cp_polydet_targets_ex,
                               cp_class_instance_masks, cp_class_writer_instances, cp_render_overlay_workspace_bytes,
-                              cp_render_overlay, cp_render_heatmap, cp_soft_nms_device, cp_merge_detections(_workspace_bytes) */
+                              cp_render_overlay, cp_render_heatmap, cp_soft_nms_device, cp_merge_detections(_workspace_bytes),
+                              cp_dcn_v2_forward_slices(_count), cp_dcn_splitk_reduce, cp_depthwise_up_forward_slices */
 
 enum {
   CP_OK = 0,
@@ -131,6 +132,25 @@ int cp_dcn_v2_forward(const cp_dcn_shape* s, const float* x, const float* offset
                       int32_t contraction, float* out, void* workspace, size_t workspace_bytes,
                       void* stream);
 
+/* The K-split launch of cp_dcn_v2_forward WITHOUT its reduce, for a consumer that adds the slices up while it reads them
+ * (cp_depthwise_up_forward_slices): no reduce launch, no map written and read back.
+ *   cp_dcn_v2_forward_slices_count: the slice count (> 1) where cp_dcn_v2_forward would run the LDS-region kernel with
+ *       its input channels split for this shape and contraction; 0 everywhere else.
+ *   cp_dcn_v2_forward_slices: cp_dcn_v2_forward's arguments without bias, epilogue and `out`.  Leaves the slices' RAW
+ *       sums (no bias, no epilogue) as partial[slice][B][Cout][H][W] in `workspace` (cp_dcn_v2_forward_workspace_bytes),
+ *       *partial_offset bytes from its start; they are valid until the next call that uses the workspace.
+ *       CP_EUNSUPPORTED where the count is 0.
+ *   cp_dcn_splitk_reduce: the reduce on its own, out[b][c][i] = act((sum_s partial[s][b][c][i]) * ep_scale[c] +
+ *       ep_shift[c]), slices added in order, NULL = scale 1 / shift 0 -- what cp_dcn_v2_forward launches after the
+ *       slices (with shift = bias where no epilogue is given). */
+int cp_dcn_v2_forward_slices_count(const cp_dcn_shape* s, int32_t contraction);
+int cp_dcn_v2_forward_slices(const cp_dcn_shape* s, const float* x, const float* offset, int64_t offset_bstride,
+                             const float* mask, int64_t mask_bstride, int32_t mask_is_logit, const float* weight,
+                             int32_t contraction, void* workspace, size_t workspace_bytes, size_t* partial_offset,
+                             void* stream);
+int cp_dcn_splitk_reduce(const float* partial, int32_t nslices, const float* ep_scale, const float* ep_shift,
+                         int32_t relu, float* out, int32_t B, int32_t C, int64_t HW, void* stream);
+
 /* The DCN module of the reference in ONE launch: `DCN.forward` (upstream DCNv2/dcn_v2.py: out = conv_offset_mask(x);
  * o1, o2, mask = chunk(out, 3); offset = cat(o1, o2); mask = sigmoid(mask); dcn_v2_conv(x, offset, mask, ...)), i.e.
  * cp_dcn_v2_forward with the 27-channel 3x3 / pad 1 convolution that produces its offsets and mask logits computed
@@ -175,6 +195,13 @@ int cp_dcn_v2_backward(const cp_dcn_shape* s, const float* x, const float* offse
  * ACCUMULATED INTO (caller zero-fills); grad_skip = grad_out is the caller's business. */
 int cp_depthwise_up_forward(const float* x, const float* weight, const float* skip, float* out,
                             int32_t B, int32_t C, int32_t H, int32_t W, int32_t f, void* stream);
+/* The same on an input that is still K-split slices (cp_dcn_v2_forward_slices):
+ *   out = up(act((sum_s partial[s]) * ep_scale[c] + ep_shift[c])) + skip,   partial[s] = partial + s * slice_stride
+ * (elements), each [B,C,H,W]; NULL scale / shift = 1 / 0.  Bit-identical to cp_dcn_splitk_reduce followed by
+ * cp_depthwise_up_forward.  f = 2 with W even, or f = 4; CP_EUNSUPPORTED otherwise (run those two). */
+int cp_depthwise_up_forward_slices(const float* partial, int32_t nslices, int64_t slice_stride, const float* ep_scale,
+                                   const float* ep_shift, int32_t relu, const float* weight, const float* skip,
+                                   float* out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t f, void* stream);
 int cp_depthwise_up_backward(const float* x, const float* weight, const float* grad_out,
                              float* grad_x, float* grad_weight, int32_t B, int32_t C, int32_t H,
                              int32_t W, int32_t f, void* stream);
