@@ -22,6 +22,9 @@ _ENABLED = True              # set by centerpoly_amd.arithmetic.configure
 _WGRAD = True
 MIN_CIN = 24                 # the contraction steps over 32 input channels: fewer would mostly multiply zeros
 MIN_WORKGROUPS = 128         # (of the narrowest tile form) below this the launch cannot fill the 256 CUs
+# conv_infer's 1x1 / stride 1 route: "auto" -- the streaming kernel at the shapes it measured faster at (_stream_wins),
+# "off" -- never (A/B runs), "force" -- at every shape it supports (tests).  The result has the same bits either way.
+STREAM_1X1 = "auto"
 
 
 def _workgroups(B, cout, H, W):
@@ -171,6 +174,45 @@ def _launch(x, wp, bias, residual, cout, relu, taps=9, stride=1):
     return out
 
 
+def _stream_wins(cin, cout, H, W):
+    """The 1x1 shapes that the streaming kernel (csrc/conv_stream.hip) measured faster at than the LDS-staged one
+    (tools/probe_conv1x1_stream.py, profiles/conv1x1_stream_probe.txt: its average below the other's fastest launch).
+    A function of (sum Cin, Cout, H, W) only, never of the batch.  Which kernel runs changes no bit of the result."""
+    return (cin, cout, H * W) in _STREAM_SHAPES
+
+
+# (sum Cin, Cout, H * W): the Roots of DLA-34 levels 3-5 at a 1024 x 2048 input.  The level-2 Root (64 + 64 -> 64
+# @256x512), the four projections (32 -> 64, 64 -> 128, 128 -> 256, 256 -> 512) and every other shape measured level or
+# were not measured: they stay where they were.
+_STREAM_SHAPES = frozenset([(256, 128, 128 * 256), (448, 128, 128 * 256), (512, 256, 64 * 128), (896, 256, 64 * 128),
+                            (1280, 512, 32 * 64)])
+
+
+def _stream_infer(xs, cs, owner, w, bias, residual, relu, slot):
+    """conv_infer's 1x1 / stride 1 launch through cp_conv1x1_stream_forward -- the bits of cp_conv_mfma_forward_strided, from
+    the same prepared weights (same slot) -- or None where STREAM_1X1 and the kernel's shape rules (every source a multiple
+    of 16 channels, 32-bit offsets within an image) do not send it there."""
+    x0 = xs[0]
+    B, _, H, W = x0.shape
+    cin, cout, n = sum(cs), w.shape[0], len(xs)
+    if not (STREAM_1X1 == "force" or _stream_wins(cin, cout, H, W)) or B > 65535:
+        return None
+    L = _C.lib()
+    chans = (_C.c_int32 * n)(*cs)
+    if not L.cp_conv1x1_stream_supported(chans, n, cout, H, W):
+        return None
+    wp, _ = prepared(owner, slot, (w,), lambda: _permute(w.contiguous(), cin, cout, 0))
+    xs = [x.contiguous() for x in xs]
+    out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x0.device)
+    ptrs = (_C.c_void_p * n)(*[x.data_ptr() for x in xs])
+    end = _C.kernel_timer.start(("conv1x1_fwd", cin, cout, H, W, B)) if _C.kernel_timer is not None else None
+    _C.check(L.cp_conv1x1_stream_forward(ptrs, chans, n, _C.ptr(wp), _C.ptr(bias), _C.ptr(residual), _C.ptr(out), B, H, W,
+                                         cout, 1 if relu else 0, _C.stream()), "cp_conv1x1_stream_forward")
+    if end is not None:
+        end.record()
+    return out
+
+
 def conv_infer(xs, owner, w, bias=None, residual=None, relu=False, conv=None, slot="conv", x_split=False,
                out_split=False):
     """Inference: 3x3 / pad 1 or 1x1 (stride 1 or 2) convolution of the channel concatenation of `xs` -- read in place,
@@ -201,6 +243,11 @@ def conv_infer(xs, owner, w, bias=None, residual=None, relu=False, conv=None, sl
     B, _, H, W = x0.shape
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     L = _C.lib()
+    if k == (1, 1) and stride == 1 and STREAM_1X1 != "off" and not (x_split or out_split) and cin == w.shape[1] \
+            and (residual is None or residual.is_contiguous()):
+        out = _stream_infer(xs, cs, owner, w, bias, residual, relu, slot)
+        if out is not None:
+            return out
     if cin != w.shape[1] or cin < MIN_CIN or (len(xs) > 1 and any(c % 32 for c in cs)) \
             or not all(L.cp_conv3x3_mfma_supported(c, cout, H, W) for c in cs) \
             or not _fills(B, cin, cout, Ho, Wo) or (residual is not None and not residual.is_contiguous()):

@@ -53,7 +53,8 @@ extern "C" {
                               Added since, backward compatible (no version change): cp_polydet_targets_ex,
                               cp_class_instance_masks, cp_class_writer_instances, cp_render_overlay_workspace_bytes,
                               cp_render_overlay, cp_render_heatmap, cp_soft_nms_device, cp_merge_detections(_workspace_bytes),
-                              cp_dcn_v2_forward_slices(_count), cp_dcn_splitk_reduce, cp_depthwise_up_forward_slices */
+                              cp_dcn_v2_forward_slices(_count), cp_dcn_splitk_reduce, cp_depthwise_up_forward_slices,
+                              cp_conv1x1_stream_* */
 
 enum {
   CP_OK = 0,
@@ -318,6 +319,27 @@ int cp_conv_mfma_forward_split(const void* x, int32_t x_split, const void* wperm
                                int32_t taps, int32_t stride, int32_t relu, void* stream);
 int cp_activation_split(const float* x, void* out, int32_t B, int32_t C, int32_t H, int32_t W, void* stream);
 int cp_activation_unsplit(const void* in, float* x, int32_t B, int32_t C, int32_t H, int32_t W, void* stream);
+/* The 1x1 / stride 1 forward convolution of cp_conv_mfma_forward (taps = 1) streamed through registers -- no LDS staging,
+ * the loads of two 32-channel chunks in flight per wave (csrc/conv_stream.hip): `Root` and `Tree.project` at inference
+ * (pose_dla_dcn.py:148-166, 206-213).  Every output element is the same sequence of floating-point operations as in
+ * cp_conv_mfma_forward: the two give the SAME BITS (same MFMA, chunk order, K split, epilogue order).
+ * Every cs[i] is a multiple of 16; byte offsets within an image are 32-bit: cp_conv1x1_stream_supported tells, anything
+ * else returns CP_EUNSUPPORTED.  wperm: cp_conv_mfma_prepare's form with taps = 1 (cp_conv1x1_stream_weight_bytes /
+ * _prepare forward to it: one prepared buffer serves both kernels).
+ * The tile form: nb pixel groups of 32 per wave (1 | 2; a function of (Cout, H * W)) and ks wave groups over
+ * interleaved chunks (1 | 2 | 4; the K split cp_conv_mfma_forward picks for (Cin, Cout, H, W, B), which is what its bits
+ * depend on).  cp_conv1x1_stream_form returns nb << 8 | ks; cp_conv1x1_stream_forward_form runs a given form (0, 0: that
+ * one; tests and probes force the others, whose K splits sum in another order). */
+int cp_conv1x1_stream_supported(const int32_t* cs, int32_t nsrc, int32_t Cout, int32_t H, int32_t W);
+size_t cp_conv1x1_stream_weight_bytes(int32_t Cin, int32_t Cout);
+int cp_conv1x1_stream_prepare(const float* weight, int32_t Cin, int32_t Cout, void* wperm, void* stream);
+int cp_conv1x1_stream_forward(const float* const* xs, const int32_t* cs, int32_t nsrc, const void* wperm, const float* bias,
+                              const float* residual, float* out, int32_t B, int32_t H, int32_t W, int32_t Cout,
+                              int32_t relu, void* stream);
+int cp_conv1x1_stream_form(int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t B);
+int cp_conv1x1_stream_forward_form(const float* const* xs, const int32_t* cs, int32_t nsrc, const void* wperm,
+                                   const float* bias, const float* residual, float* out, int32_t B, int32_t H, int32_t W,
+                                   int32_t Cout, int32_t relu, int32_t nb, int32_t ks, void* stream);
 /* Weight gradient of a 3x3 / stride 2 / pad 1 convolution (the first convolution of DLA levels 2-5,
  * src/lib/models/networks/pose_dla_dcn.py:32-40; cuDNN's backward-filter in the reference), same arithmetic:
  *   gw[co][ci][ky][kx] += sum_{b,i,j} grad_out[b][co][i][j] * x[b][ci][2 i + ky - 1][2 j + kx - 1]
