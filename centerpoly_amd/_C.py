@@ -144,6 +144,10 @@ _SIGNATURES = {
     "cp_conv1x1_stream_forward": (c_int32, [_P, _P, c_int32, _P, _P, _P, _P] + [c_int32] * 5 + [_P]),
     "cp_conv1x1_stream_form": (c_int32, [c_int32] * 5),
     "cp_conv1x1_stream_forward_form": (c_int32, [_P, _P, c_int32, _P, _P, _P, _P] + [c_int32] * 7 + [_P]),
+    "cp_conv3x3_stream_supported": (c_int32, [c_int32] * 4),
+    "cp_conv3x3_stream_form": (c_int32, [c_int32] * 5),
+    "cp_conv3x3_stream_forward": (c_int32, [_P] * 5 + [c_int32] * 6 + [_P]),
+    "cp_conv3x3_stream_forward_form": (c_int32, [_P] * 5 + [c_int32] * 8 + [_P]),
     "cp_conv_mfma_input_grad_relu_workspace_bytes": (c_size_t, [c_int32] * 4),
     "cp_conv_mfma_input_grad_relu": (c_int32, [_P] * 5 + [c_int32] * 6 + [_P, c_size_t, _P]),
     "cp_conv3x3_s2_input_grad": (c_int32, [_P, _P, _P, _P] + [c_int32] * 5 + [_P]),

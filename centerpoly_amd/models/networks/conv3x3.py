@@ -25,6 +25,9 @@ MIN_WORKGROUPS = 128         # (of the narrowest tile form) below this the launc
 # conv_infer's 1x1 / stride 1 route: "auto" -- the streaming kernel at the shapes it measured faster at (_stream_wins),
 # "off" -- never (A/B runs), "force" -- at every shape it supports (tests).  The result has the same bits either way.
 STREAM_1X1 = "auto"
+# conv_infer's 3x3 / stride 1 route to <= 32 output channels (the DCN offset convolutions): the same three settings, the
+# same rule (_stream3_wins), the same bits either way.
+STREAM_3X3 = "auto"
 
 
 def _workgroups(B, cout, H, W):
@@ -213,6 +216,43 @@ def _stream_infer(xs, cs, owner, w, bias, residual, relu, slot):
     return out
 
 
+def _stream3_wins(cin, cout, H, W):
+    """The 3x3 shapes that the streaming kernel (csrc/conv3x3_stream.hip) measured faster at than the LDS-staged one
+    (tools/probe_conv3x3_stream.py, profiles/conv3x3_stream_probe.txt: its average below the other's fastest launch).
+    A function of (Cin, Cout, H, W) only, never of the batch.  Which kernel runs changes no bit of the result."""
+    return (cin, cout, H * W) in _STREAM3_SHAPES
+
+
+# (Cin, Cout, H * W): the conv_offset_mask of the eleven DCN modules of DLA-34 that do not take the fused module launch at
+# a 1024 x 2048 input -- probe: 13.5 us against 21.0 (64 x 128), 14.4 against 33.1 (32 x 64), 14.9 against 16.0 / 15.4
+# fastest (128 x 256: in by 0.5 us there; 12.4 against 17.4 inside the step,
+# profiles/conv3x3_stream_infer_by_launch_shape_after.csv).  Nothing else was measured: every other shape stays where
+# it was.
+_STREAM3_SHAPES = frozenset([(128, 27, 128 * 256), (256, 27, 64 * 128), (512, 27, 32 * 64)])
+
+
+def _stream3_infer(x, owner, w, bias, slot):
+    """conv_infer's 3x3 / stride 1 / one source / <= 32 channels / bias-only launch through cp_conv3x3_stream_forward --
+    the bits of cp_conv_mfma_forward_strided, from the same prepared weights (same slot) -- or None where STREAM_3X3 and
+    the kernel's shape rules do not send it there."""
+    B, cin, H, W = x.shape
+    cout = w.shape[0]
+    if not (STREAM_3X3 == "force" or _stream3_wins(cin, cout, H, W)) or B > 65535:
+        return None
+    L = _C.lib()
+    if not L.cp_conv3x3_stream_supported(cin, cout, H, W):
+        return None
+    wp, _ = prepared(owner, slot, (w,), lambda: _permute(w.contiguous(), cin, cout, 0))
+    x = x.contiguous()
+    out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    end = _C.kernel_timer.start(("conv3x3_fwd", cin, cout, H, W, B)) if _C.kernel_timer is not None else None
+    _C.check(L.cp_conv3x3_stream_forward(_C.ptr(x), _C.ptr(wp), _C.ptr(bias), None, _C.ptr(out), B, cin, H, W, cout, 0,
+                                         _C.stream()), "cp_conv3x3_stream_forward")
+    if end is not None:
+        end.record()
+    return out
+
+
 def conv_infer(xs, owner, w, bias=None, residual=None, relu=False, conv=None, slot="conv", x_split=False,
                out_split=False):
     """Inference: 3x3 / pad 1 or 1x1 (stride 1 or 2) convolution of the channel concatenation of `xs` -- read in place,
@@ -253,6 +293,11 @@ def conv_infer(xs, owner, w, bias=None, residual=None, relu=False, conv=None, sl
             or not _fills(B, cin, cout, Ho, Wo) or (residual is not None and not residual.is_contiguous()):
         return None
     taps = k[0] * k[1]
+    if k == (3, 3) and stride == 1 and len(xs) == 1 and cout <= 32 and residual is None and not relu \
+            and not (x_split or out_split) and STREAM_3X3 != "off":
+        out = _stream3_infer(x0, owner, w, bias, slot)
+        if out is not None:
+            return out
     wp, _ = prepared(owner, slot, (w,), lambda: _permute(w.contiguous(), cin, cout, 0))
     xs = [x.contiguous() for x in xs]
     out = torch.empty((B, cout, Ho, Wo), dtype=torch.float32, device=x0.device)

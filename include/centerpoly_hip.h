@@ -54,7 +54,7 @@ extern "C" {
                               cp_class_instance_masks, cp_class_writer_instances, cp_render_overlay_workspace_bytes,
                               cp_render_overlay, cp_render_heatmap, cp_soft_nms_device, cp_merge_detections(_workspace_bytes),
                               cp_dcn_v2_forward_slices(_count), cp_dcn_splitk_reduce, cp_depthwise_up_forward_slices,
-                              cp_conv1x1_stream_* */
+                              cp_conv1x1_stream_*, cp_conv3x3_stream_* */
 
 enum {
   CP_OK = 0,
@@ -340,6 +340,26 @@ int cp_conv1x1_stream_form(int32_t Cin, int32_t Cout, int32_t H, int32_t W, int3
 int cp_conv1x1_stream_forward_form(const float* const* xs, const int32_t* cs, int32_t nsrc, const void* wperm,
                                    const float* bias, const float* residual, float* out, int32_t B, int32_t H, int32_t W,
                                    int32_t Cout, int32_t relu, int32_t nb, int32_t ks, void* stream);
+/* The 3x3 / stride 1 / pad 1 forward convolution of cp_conv_mfma_forward (taps = 9) for ONE source and Cout <= 32, + bias,
+ * streamed through registers -- no LDS staging, no barrier in the K loop, the loads of several taps in flight per wave
+ * (csrc/conv3x3_stream.hip): DCN.conv_offset_mask at inference (DCNv2/dcn_v2.py:137-145).  Every output element is the
+ * same sequence of floating-point operations as in cp_conv_mfma_forward: the two give the SAME BITS (same MFMA, chunk and
+ * tap order, K split, halo multiplied as zeros, epilogue).
+ * Byte offsets within an image are 32-bit: cp_conv3x3_stream_supported tells.  Cout > 32, an unsupported shape, a
+ * residual or relu != 0 return CP_EUNSUPPORTED and launch nothing (the caller keeps cp_conv_mfma_forward).
+ * wperm: cp_conv_mfma_prepare's form with taps = 9 (one prepared buffer serves both kernels).
+ * The tile form: nt tiles of 16 pixels per wave (1 | 2 | 4; a function of (H, W); 4 on a width that is a multiple of 4
+ * is the row form: 64 consecutive pixels per wave, 16-byte loads, the taps of a row from one split) and ks wave groups over
+ * interleaved chunks (1 | 2 | 4; the K split cp_conv_mfma_forward picks for (Cin, Cout, H, W, B), which is what its bits
+ * depend on).  cp_conv3x3_stream_form returns nt << 8 | ks; cp_conv3x3_stream_forward_form runs a given form (0, 0: that
+ * one; tests and probes force the others, whose K splits sum in another order). */
+int cp_conv3x3_stream_supported(int32_t Cin, int32_t Cout, int32_t H, int32_t W);
+int cp_conv3x3_stream_form(int32_t Cin, int32_t Cout, int32_t H, int32_t W, int32_t B);
+int cp_conv3x3_stream_forward(const float* x, const void* wperm, const float* bias, const float* residual, float* out,
+                              int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout, int32_t relu, void* stream);
+int cp_conv3x3_stream_forward_form(const float* x, const void* wperm, const float* bias, const float* residual, float* out,
+                                   int32_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout, int32_t relu, int32_t nt,
+                                   int32_t ks, void* stream);
 /* Weight gradient of a 3x3 / stride 2 / pad 1 convolution (the first convolution of DLA levels 2-5,
  * src/lib/models/networks/pose_dla_dcn.py:32-40; cuDNN's backward-filter in the reference), same arithmetic:
  *   gw[co][ci][ky][kx] += sum_{b,i,j} grad_out[b][co][i][j] * x[b][ci][2 i + ky - 1][2 j + kx - 1]
