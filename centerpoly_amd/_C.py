@@ -81,6 +81,7 @@ _SIGNATURES = {
     "cp_channel_sum_accumulate": (c_int32, [_P, _P, c_int32, c_int32, c_int64, _P]),
     "cp_bias_relu_backward": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int64, _P]),
     "cp_preprocess_warp_normalize": (c_int32, [_P, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
+    "cp_preprocess_warp_normalize_batch": (c_int32, [_P] * 6 + [c_int32] * 4 + [_P, _P]),
     "cp_color_aug_workspace_bytes": (c_size_t, []),
     "cp_color_aug_normalize": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "cp_sample_inputs_workspace_bytes": (c_size_t, [c_int32] * 3),

@@ -15,6 +15,10 @@
 //
 // HBM-bound: reads 3 B/px of the source window once (neighbouring lanes share the 2x2 taps
 // through L1), writes 12 B/px (24 with the flipped copy), coalesced per channel plane.
+// cp_preprocess_warp_normalize_batch does the same for B sources of different sizes laid back to back (the
+// detector's run_batch): blockIdx.z is the image, its parameters travel in the kernel arguments, one launch per 16
+// images, the same bytes per output pixel; all originals first in `out`, then all flipped copies.  The tap
+// arithmetic is stated once (warp_tap_u8), so image b has the bits of the single-image call.
 //
 // (2) Post-processing: polydet_post_process's transform_preds (reference:
 // src/lib/utils/post_process.py:105-122, src/lib/utils/image.py:19-24,62-65) -- the inverse
@@ -34,36 +38,91 @@ struct PreArgs {
   int sh, sw, dh, dw, flip;
 };
 
-__global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) {
-  const int x = blockIdx.x * 256 + threadIdx.x;
-  const int y = blockIdx.y;
-  if (x >= a.dw) return;
+// cv2's 8-bit bilinear tap of output pixel (x, y) under the inverse map m, constant border 0: the three channel
+// values as remapBilinear rounds them (<= 255).  Integer work after the float64 coordinates.  The one statement of
+// the arithmetic in this file: preprocess_kernel and preprocess_batch_kernel both call it.
+__device__ __forceinline__ void warp_tap_u8(const double* m, const uint8_t* src, int sh, int sw, int x, int y,
+                                            int v[3]) {
   // explicit rn ops: the compiler must not contract M1*y + M2 into an fma
-  const long long X0 = cp_round_fix(__dadd_rn(__dmul_rn(a.m[1], (double)y), a.m[2])) + 16;
-  const long long Y0 = cp_round_fix(__dadd_rn(__dmul_rn(a.m[4], (double)y), a.m[5])) + 16;
-  const long long X = (X0 + cp_round_fix(__dmul_rn(a.m[0], (double)x))) >> 5;
-  const long long Y = (Y0 + cp_round_fix(__dmul_rn(a.m[3], (double)x))) >> 5;
+  const long long X0 = cp_round_fix(__dadd_rn(__dmul_rn(m[1], (double)y), m[2])) + 16;
+  const long long Y0 = cp_round_fix(__dadd_rn(__dmul_rn(m[4], (double)y), m[5])) + 16;
+  const long long X = (X0 + cp_round_fix(__dmul_rn(m[0], (double)x))) >> 5;
+  const long long Y = (Y0 + cp_round_fix(__dmul_rn(m[3], (double)x))) >> 5;
   const int sx = (int)min(max(X >> 5, -32768ll), 32767ll);   // saturate_cast<short>
   const int sy = (int)min(max(Y >> 5, -32768ll), 32767ll);
   const int fx = (int)(X & 31), fy = (int)(Y & 31);
   const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32;
   const int w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
-  const bool y0 = sy >= 0 && sy < a.sh, y1 = sy + 1 >= 0 && sy + 1 < a.sh;
-  const bool x0 = sx >= 0 && sx < a.sw, x1 = sx + 1 >= 0 && sx + 1 < a.sw;
-  const uint8_t* r0 = a.src + ((long long)(y0 ? sy : 0) * a.sw) * 3;
-  const uint8_t* r1 = a.src + ((long long)(y1 ? sy + 1 : 0) * a.sw) * 3;
+  const bool y0 = sy >= 0 && sy < sh, y1 = sy + 1 >= 0 && sy + 1 < sh;
+  const bool x0 = sx >= 0 && sx < sw, x1 = sx + 1 >= 0 && sx + 1 < sw;
+  const uint8_t* r0 = src + ((long long)(y0 ? sy : 0) * sw) * 3;
+  const uint8_t* r1 = src + ((long long)(y1 ? sy + 1 : 0) * sw) * 3;
   const int c0 = (x0 ? sx : 0) * 3, c1 = (x1 ? sx + 1 : 0) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int p00 = (y0 && x0) ? r0[c0 + c] : 0, p01 = (y0 && x1) ? r0[c1 + c] : 0;
+    const int p10 = (y1 && x0) ? r1[c0 + c] : 0, p11 = (y1 && x1) ? r1[c1 + c] : 0;
+    v[c] = (w00 * p00 + w01 * p01 + w10 * p10 + w11 * p11 + (1 << 14)) >> 15;   // <= 255
+  }
+}
+
+// the numpy normalisation in float64, cast to fp32 once
+__device__ __forceinline__ float normalize_u8(int v, double mean, double stdv) {
+  return (float)__ddiv_rn(__dsub_rn(__ddiv_rn((double)v, 255.0), mean), stdv);
+}
+
+__global__ __launch_bounds__(256) void preprocess_kernel(PreArgs a) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  const int y = blockIdx.y;
+  if (x >= a.dw) return;
+  int v[3];
+  warp_tap_u8(a.m, a.src, a.sh, a.sw, x, y, v);
   const long long plane = (long long)a.dh * a.dw;
   float* o = a.out + (long long)y * a.dw + x;
   float* of = a.out + 3 * plane + (long long)y * a.dw + (a.dw - 1 - x);
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
-    const int p00 = (y0 && x0) ? r0[c0 + c] : 0, p01 = (y0 && x1) ? r0[c1 + c] : 0;
-    const int p10 = (y1 && x0) ? r1[c0 + c] : 0, p11 = (y1 && x1) ? r1[c1 + c] : 0;
-    const int v = (w00 * p00 + w01 * p01 + w10 * p10 + w11 * p11 + (1 << 14)) >> 15;   // <= 255
-    const float f = (float)__ddiv_rn(__dsub_rn(__ddiv_rn((double)v, 255.0), a.mean[c]), a.stdv[c]);
+    const float f = normalize_u8(v[c], a.mean[c], a.stdv[c]);
     o[c * plane] = f;
     if (a.flip) of[c * plane] = f;
+  }
+}
+
+// ---- the same for a batch of sources of different sizes (cp_preprocess_warp_normalize_batch) ----
+// blockIdx.z is the image within the chunk; its inverse matrix, byte offset and size travel by value in the
+// kernel arguments, PB_CHUNK images per launch (16 x 64 B), so nothing is copied to the device inside the call.
+constexpr int PB_CHUNK = 16;
+
+struct PreBatchImage {
+  double m[6];            // inverse map dst -> src
+  long long offset;       // bytes from `images` to this source
+  int sh, sw;
+};
+
+struct PreBatchArgs {
+  const uint8_t* images;
+  float* out;             // image 0 of the chunk
+  float* out_flip;        // its mirrored copy (batch images further on), or null
+  double mean[3], stdv[3];
+  int dh, dw;
+  PreBatchImage im[PB_CHUNK];
+};
+
+__global__ __launch_bounds__(256) void preprocess_batch_kernel(PreBatchArgs a) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  const int y = blockIdx.y;
+  if (x >= a.dw) return;
+  const PreBatchImage& p = a.im[blockIdx.z];
+  int v[3];
+  warp_tap_u8(p.m, a.images + p.offset, p.sh, p.sw, x, y, v);
+  const long long plane = (long long)a.dh * a.dw;
+  const long long img = (long long)blockIdx.z * 3 * plane;
+  float* o = a.out + img + (long long)y * a.dw + x;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float f = normalize_u8(v[c], a.mean[c], a.stdv[c]);
+    o[c * plane] = f;
+    if (a.out_flip) a.out_flip[img + c * plane + (long long)y * a.dw + (a.dw - 1 - x)] = f;
   }
 }
 
@@ -126,6 +185,42 @@ extern "C" int cp_preprocess_warp_normalize(const uint8_t* src, int32_t src_h, i
   a.sh = src_h; a.sw = src_w; a.dh = dst_h; a.dw = dst_w; a.flip = flip_copy ? 1 : 0;
   hipLaunchKernelGGL(preprocess_kernel, dim3((dst_w + 255) / 256, dst_h), dim3(256), 0,
                      (hipStream_t)stream, a);
+  return cp_launch_status();
+}
+
+extern "C" int cp_preprocess_warp_normalize_batch(const uint8_t* images, const int64_t* image_offset,
+                                                  const int32_t* image_hw, const double* trans,
+                                                  const float* mean, const float* stdv, int32_t batch,
+                                                  int32_t dst_h, int32_t dst_w, int32_t flip_copy, float* out,
+                                                  void* stream) {
+  // the host tables first, so that a refusal never depends on what the device pointers are
+  CP_CHECK_ARG(image_offset && image_hw && trans && mean && stdv);
+  CP_CHECK_ARG(batch > 0 && dst_h > 0 && dst_w > 0);
+  for (int b = 0; b < batch; ++b)
+    CP_CHECK_ARG(image_hw[2 * b] > 0 && image_hw[2 * b + 1] > 0 && image_offset[b] >= 0);
+  if (dst_h > 65535) return CP_EUNSUPPORTED;
+  for (int b = 0; b < batch; ++b)
+    if (image_hw[2 * b] > 32767 || image_hw[2 * b + 1] > 32767) return CP_EUNSUPPORTED;
+  CP_CHECK_ARG(images && out);
+  const long long HW = (long long)dst_h * dst_w;
+  PreBatchArgs a;
+  a.images = images; a.dh = dst_h; a.dw = dst_w;
+  for (int c = 0; c < 3; ++c) { a.mean[c] = (double)mean[c]; a.stdv[c] = (double)stdv[c]; }
+  for (int first = 0; first < batch; first += PB_CHUNK) {
+    const int n = batch - first < PB_CHUNK ? batch - first : PB_CHUNK;
+    a.out = out + (long long)first * 3 * HW;
+    a.out_flip = flip_copy ? out + ((long long)batch + first) * 3 * HW : nullptr;
+    for (int i = 0; i < PB_CHUNK; ++i) {
+      const int b = first + (i < n ? i : 0);                    // unused slots repeat the chunk's first image
+      PreBatchImage& p = a.im[i];
+      // cv::warpAffine inverts the forward map in place, in float64
+      cp_invert_affine(trans + 6 * b, p.m);
+      p.offset = image_offset[b];
+      p.sh = image_hw[2 * b]; p.sw = image_hw[2 * b + 1];
+    }
+    hipLaunchKernelGGL(preprocess_batch_kernel, dim3((dst_w + 255) / 256, dst_h, n), dim3(256), 0,
+                       (hipStream_t)stream, a);
+  }
   return cp_launch_status();
 }
 

@@ -58,6 +58,25 @@ def _first(batch):
     return batch[0]
 
 
+def group(items, n, same_size=False):
+    """Lists of up to `n` consecutive items, in order, for `detector.run_batch` (test.py --test_batch_size); the last
+    may be short.  An item is an image array or a dict with one under "image".  same_size (--keep_res, where the
+    network input follows the source): a group also ends where the next image's (h, w) differs from its first's.
+    Pure host, nothing is copied: the loader's workers keep decoding ahead, one image each."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("group size must be at least 1 (got %d)" % n)
+    size = lambda item: tuple((item["image"] if isinstance(item, dict) else item).shape[:2])
+    current = []
+    for item in items:
+        if current and (len(current) == n or (same_size and size(item) != size(current[0]))):
+            yield current
+            current = []
+        current.append(item)
+    if current:
+        yield current
+
+
 def iterate(images, prefetch, num_workers):
     """The items in order: a plain loop, or a DataLoader whose `num_workers` workers decode ahead of the consumer
     (batches of one, handed over as they are: the arrays are not collated into tensors)."""

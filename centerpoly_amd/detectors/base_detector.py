@@ -13,6 +13,10 @@ path is read through PIL into cv2.imread's layout (8-bit BGR).
 --debug >= 1 (reference :108-109, 145-146, 186-187): run() draws the detections on the
 device (utils/debugger.py), writes the pictures into opt.debug_dir and returns the
 overlay as ret['vis']; at --debug 0 no Debugger exists and nothing else changes.
+
+Beyond the reference: .run_batch(images) sends a list of images through the network together
+(.pre_process_batch: one cp_preprocess_warp_normalize_batch launch for the whole list) and
+returns run()'s dict with one `results` entry per image and 'n' (DESIGN 4.26).
 """
 import os
 import time
@@ -21,7 +25,7 @@ import numpy as np
 import torch
 
 from ..models.model import create_model, load_model
-from ..utils.image import get_affine_transform, warp_affine_normalize
+from ..utils.image import get_affine_transform, warp_affine_normalize, warp_affine_normalize_batch
 
 
 def read_image_bgr(path):
@@ -79,8 +83,9 @@ class BaseDetector(object):
         self.pause = True
         self.debugger = None                                 # made at the first run() with --debug >= 1, then kept
 
-    def pre_process(self, image, scale, meta=None):
-        height, width = image.shape[0:2]
+    def _input_geometry(self, height, width, scale):
+        """(new_height, new_width, inp_height, inp_width, c, s, trans_input) of an image of height x width at a test
+        scale (reference :66-83)."""
         new_height, new_width = int(height * scale), int(width * scale)
         if self.opt.fix_res:
             inp_height, inp_width = self.opt.input_h, self.opt.input_w
@@ -92,6 +97,11 @@ class BaseDetector(object):
             c = np.array([new_width // 2, new_height // 2], dtype=np.float32)
             s = np.array([inp_width, inp_height], dtype=np.float32)
         trans_input = get_affine_transform(c, s, 0, [inp_width, inp_height])
+        return new_height, new_width, inp_height, inp_width, c, s, trans_input
+
+    def pre_process(self, image, scale, meta=None):
+        height, width = image.shape[0:2]
+        new_height, new_width, inp_height, inp_width, c, s, trans_input = self._input_geometry(height, width, scale)
         src = self._upload(image)
         if (new_height, new_width) != (height, width):
             src = _resize_bilinear_u8(src, new_width, new_height)
@@ -101,13 +111,49 @@ class BaseDetector(object):
                 "out_width": inp_width // self.opt.down_ratio}
         return images, meta
 
+    def pre_process_batch(self, images, scale):
+        """pre_process for a list of 8-bit images in one launch: ([(1 + flip_test) * B, 3, inp_h, inp_w], [meta per
+        image]), all originals first, then all flipped copies.  Every image is uploaded into its slice of one device
+        buffer (no host-side concatenation) and warped by cp_preprocess_warp_normalize_batch with its own c, s and
+        trans_input, the ones pre_process computes.  The images of a batch must share (inp_height, inp_width): always
+        under --fix_res, under --keep_res only for equal source sizes (ValueError otherwise, before any launch)."""
+        for image in images:
+            self._check_image(image)
+        geo = [self._input_geometry(im.shape[0], im.shape[1], scale) for im in images]
+        if not geo:
+            raise ValueError("pre_process_batch needs at least one image")
+        if len(set(g[2:4] for g in geo)) > 1:
+            raise ValueError("the images of a batch must give one network input size; sources %s give inputs %s "
+                             "(--keep_res batches need equal source sizes)"
+                             % ([tuple(im.shape[:2]) for im in images], [g[2:4] for g in geo]))
+        inp_height, inp_width = geo[0][2:4]
+        hw = np.array([g[0:2] for g in geo], dtype=np.int32)
+        sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
+        offset = np.cumsum(sizes) - sizes
+        flat = torch.empty(int(sizes.sum()), dtype=torch.uint8, device=self.opt.device)
+        for image, g, off, n in zip(images, geo, offset, sizes):
+            dst = flat[int(off): int(off + n)]
+            if tuple(g[0:2]) != tuple(image.shape[0:2]):
+                dst.copy_(_resize_bilinear_u8(self._upload(image), g[1], g[0]).view(-1))
+            else:
+                dst.copy_(torch.from_numpy(np.ascontiguousarray(image).reshape(-1)))
+        out = warp_affine_normalize_batch(flat, hw, offset, np.stack([g[6].reshape(6) for g in geo]), self.mean,
+                                          self.std, inp_height, inp_width, flip_copy=bool(self.opt.flip_test))
+        metas = [{"c": g[4], "s": g[5], "out_height": inp_height // self.opt.down_ratio,
+                  "out_width": inp_width // self.opt.down_ratio} for g in geo]
+        return out, metas
+
+    @staticmethod
+    def _check_image(image):
+        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+            raise TypeError("pre_process needs an 8-bit [H,W,3] image (got %s %s)"
+                            % (image.dtype, image.shape))
+
     def _upload(self, image):
         """8-bit HWC image -> device.  A plain (pageable) copy: measured on MI355X it costs
         0.17 ms for a 2048x1024 image and is steady, while staging through a pinned buffer with
         a non-blocking copy showed periodic ~90 ms stalls (tools/probe_stalls.py)."""
-        if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
-            raise TypeError("pre_process needs an 8-bit [H,W,3] image (got %s %s)"
-                            % (image.dtype, image.shape))
+        self._check_image(image)
         return torch.from_numpy(np.ascontiguousarray(image)).to(self.opt.device)
 
     def process(self, images, return_time=False):
@@ -122,6 +168,14 @@ class BaseDetector(object):
     def merge(self, detections):
         """What run() makes its `results` with: merge_outputs, unless a detector kept its detections on the device."""
         return self.merge_outputs(detections)
+
+    def post_process_batch(self, dets, metas, scale=1):
+        """post_process for the [B, K, ncols] detections of a batch with one meta per image."""
+        raise NotImplementedError
+
+    def merge_batch(self, detections):
+        """merge for a batch: detections[scale] is what post_process_batch returned; one `results` dict per image."""
+        raise NotImplementedError
 
     def debug(self, debugger, images, dets, output, scale=1):
         raise NotImplementedError
@@ -204,3 +258,51 @@ class BaseDetector(object):
             ret["vis_files"] = debugger.show_all_imgs(pause=self.pause, path=self.opt.debug_dir, prefix=stem + "_")
             ret["vis_time"] = time.time() - end_time
         return ret
+
+    def run_batch(self, images):
+        """run() for a list of images (arrays or paths) that go through the network together: {"results": [what run()
+        returns as "results", one per image], "n": B, "tot", "load", "pre", "net", "dec", "post", "merge"}, the times
+        for the whole batch.  The batch kernels restate the per-image ones bit for bit; the network chooses some K
+        splits by its launch size, so its heads agree with a single-image launch to rounding, not in every bit.  The
+        debug pictures stay with run(): --debug >= 1 and more than one image is a ValueError."""
+        images = list(images)
+        if not images:
+            raise ValueError("run_batch needs at least one image")
+        if getattr(self.opt, "debug", 0) >= 1 and len(images) > 1:
+            raise ValueError("run_batch draws no debug pictures: with --debug %d send the images through run() one "
+                             "at a time" % self.opt.debug)
+        before = torch.backends.cudnn.deterministic
+        torch.backends.cudnn.deterministic = True
+        try:
+            return self._run_batch(images)
+        finally:
+            torch.backends.cudnn.deterministic = before
+
+    def _run_batch(self, images):
+        pre_time = net_time = dec_time = post_time = 0
+        start_time = time.time()
+        images = [load_image(im) if isinstance(im, str) else im for im in images]
+        for im in images:
+            if not isinstance(im, np.ndarray):
+                raise TypeError("run_batch takes 8-bit [H,W,3] arrays or paths (got %s)" % type(im).__name__)
+        loaded_time = time.time()
+        detections = []
+        for scale in self.scales:
+            scale_start_time = time.time()
+            batch, metas = self.pre_process_batch(images, scale)
+            torch.cuda.synchronize()
+            pre_process_time = time.time()
+            pre_time += pre_process_time - scale_start_time
+            output, dets, forward_time = self.process(batch, return_time=True)
+            torch.cuda.synchronize()
+            net_time += forward_time - pre_process_time
+            decode_time = time.time()
+            dec_time += decode_time - forward_time
+            detections.append(self.post_process_batch(dets, metas, scale))
+            post_process_time = time.time()
+            post_time += post_process_time - decode_time
+        results = self.merge_batch(detections)
+        end_time = time.time()
+        return {"results": results, "n": len(images), "tot": end_time - start_time, "load": loaded_time - start_time,
+                "pre": pre_time, "net": net_time, "dec": dec_time, "post": post_time,
+                "merge": end_time - post_process_time}

@@ -21,6 +21,7 @@ class PolydetDetector(BaseDetector):
     # 0.349 against 0.364 ms and 0.529 against 0.581 ms.
     device_merge = True
     _slot, _merged = 0, False
+    _batch = None                                    # the last run_batch's per-image rows and results (None after run)
 
     def __init__(self, opt):
         super(PolydetDetector, self).__init__(opt)
@@ -33,9 +34,10 @@ class PolydetDetector(BaseDetector):
             pseudo_depth = output["pseudo_depth"]
             reg = output["reg"] if self.opt.reg_offset else None
             if self.opt.flip_test:
-                hm = (hm[0:1] + flip_tensor(hm[1:2])) / 2
-                reg = reg[0:1] if reg is not None else None
-                polys, pseudo_depth = polys[0:1], pseudo_depth[0:1]
+                n = hm.shape[0] // 2                 # all originals, then all flipped copies (run: n = 1)
+                hm = (hm[:n] + flip_tensor(hm[n:])) / 2
+                reg = reg[:n] if reg is not None else None
+                polys, pseudo_depth = polys[:n], pseudo_depth[:n]
             torch.cuda.synchronize()
             forward_time = time.time()
             dets = polydet_decode(hm, polys, pseudo_depth, reg=reg,
@@ -48,7 +50,14 @@ class PolydetDetector(BaseDetector):
     def run(self, image_or_path_or_tensor, id=1, meta=None):
         self._slot = 0                               # the scale post_process writes next (device merge)
         self._merged = False
+        self._batch = None
         return super(PolydetDetector, self).run(image_or_path_or_tensor, id, meta)
+
+    def run_batch(self, images):
+        self._slot = 0
+        self._merged = False
+        self._batch = None
+        return super(PolydetDetector, self).run_batch(images)
 
     def _merge_on_device(self, K):
         """Several scales or --nms (the settings in which merge_outputs does real work), the switch on and the rows
@@ -81,21 +90,66 @@ class PolydetDetector(BaseDetector):
         self.rows_host = host[0]                     # ... and as they were copied back, class column included
         return ret[0]
 
-    def device_rows(self, results=None):
+    def post_process_batch(self, dets, metas, scale=1):
+        """post_process for a batch: dets [B, K, ncols], one meta per image.  One cp_polydet_post_process launch with
+        the B inverse maps either way.  One scale without --nms: one device -> host copy of [B, K, ncols], the class
+        split per image (returns the list of per-image dicts).  Several scales or --nms: the rows go into this
+        scale's slot of a [B, S, K, ncols] device buffer, image b's scales contiguous for cp_merge_detections
+        (returns None; merge_batch reads the buffer)."""
+        dets = dets.detach().contiguous()
+        B, K, ncols = dets.shape
+        c, s = [m["c"] for m in metas], [m["s"] for m in metas]
+        h, w = metas[0]["out_height"], metas[0]["out_width"]
+        if self._merge_on_device(K):
+            S = len(self.scales)
+            if self._slot >= S or self._slot == 0:
+                self._slot = 0
+                self.scale_rows = torch.empty((B, S, K, ncols), dtype=torch.float32, device=dets.device)
+            if tuple(self.scale_rows.shape) != (B, S, K, ncols):
+                raise ValueError("the test scales differ in the shape of their detections")
+            rows = torch.empty_like(dets)
+            trans = _inverse_transforms(c, s, h, w, dets.device)
+            _C.check(_C.lib().cp_polydet_post_process(_C.ptr(dets), _C.ptr(trans), float(scale), B, K, ncols,
+                                                      _C.ptr(rows), _C.stream()), "cp_polydet_post_process")
+            self.scale_rows[:, self._slot].copy_(rows)
+            self._slot += 1
+            return None
+        ret, rows, host = polydet_post_process_device(dets, c, s, h, w, self.opt.num_classes, scale,
+                                                      return_device=True, return_host=True)
+        self._batch = {"rows_dev": list(rows), "rows_host": list(host), "results": None}
+        return ret
+
+    def _image_rows(self, results, image):
+        """(rows kept by the last run / run_batch for `image` or None, the results to build them from otherwise)."""
+        kept = (len(self.scales) == 1 and not self.opt.nms) or self._merged
+        if self._batch is None:
+            if image != 0:
+                raise IndexError("image %d: the last call was run(), which holds one image" % image)
+            return ((self.rows_dev, self.rows_host) if kept else None), results
+        if not 0 <= image < len(self._batch["results"]):
+            raise IndexError("image %d: the last run_batch held %d images" % (image, len(self._batch["results"])))
+        if kept:
+            return (self._batch["rows_dev"][image], self._batch["rows_host"][image]), results
+        return None, (results if results is not None else self._batch["results"][image])
+
+    def device_rows(self, results=None, image=0):
         """The detections of the last run() as device rows [R, 2N+7] (x1,y1,x2,y2,score,cls,poly,depth), what
         CityscapesWriterMixin.score_instances_device reads.  One scale without --nms: the rows post_process left
         on the device, no copy.  Several scales or --nms: the table merge_outputs_device left there, no copy; where
-        merge_outputs ran on the host instead (device_merge off, or beyond its limits), its `results` are uploaded."""
-        if (len(self.scales) == 1 and not self.opt.nms) or self._merged:
-            return self.rows_dev
+        merge_outputs ran on the host instead (device_merge off, or beyond its limits), its `results` are uploaded.
+        After run_batch: the same for image `image` of the batch (`results` defaults to that image's)."""
+        kept, results = self._image_rows(results, image)
+        if kept is not None:
+            return kept[0]
         rows = [np.concatenate([r[:, :5], np.full((len(r), 1), j - 1, np.float32), r[:, 5:]], axis=1)
                 for j, r in sorted(results.items())]
         return torch.from_numpy(np.ascontiguousarray(np.concatenate(rows, axis=0), np.float32)).to(self.opt.device)
 
-    def host_rows(self, results=None):
+    def host_rows(self, results=None, image=0):
         """The rows of device_rows on the host, row for row (the labels of the overlay are made from them)."""
-        if (len(self.scales) == 1 and not self.opt.nms) or self._merged:
-            return self.rows_host
+        kept, results = self._image_rows(results, image)
+        if kept is not None:
+            return kept[1]
         rows = [np.concatenate([r[:, :5], np.full((len(r), 1), j - 1, np.float32), r[:, 5:]], axis=1)
                 for j, r in sorted(results.items())]
         return np.ascontiguousarray(np.concatenate(rows, axis=0), np.float32)
@@ -125,12 +179,29 @@ class PolydetDetector(BaseDetector):
             return self.merge_outputs_device()
         return self.merge_outputs(detections)
 
-    def merge_outputs_device(self):
+    def merge_batch(self, detections):
+        """One `results` dict per image of the batch: cp_merge_detections on image b's contiguous [S, K, ncols] slice
+        where post_process_batch left the scales on the device, merge_outputs on the host otherwise."""
+        if self._slot > 0:
+            kept = {"rows_dev": [], "rows_host": [], "results": []}
+            for rows in self.scale_rows:
+                kept["results"].append(self.merge_outputs_device(rows))
+                kept["rows_dev"].append(self.rows_dev)
+                kept["rows_host"].append(self.rows_host)
+            self._batch = kept
+            return kept["results"]
+        results = [self.merge_outputs([d[b] for d in detections]) for b in range(len(detections[0]))]
+        if self._batch is None:                      # the host merge of several scales or --nms: nothing kept per image
+            self._batch = {"rows_dev": None, "rows_host": None, "results": results}
+        self._batch["results"] = results
+        return results
+
+    def merge_outputs_device(self, rows=None):
         """merge_outputs on the rows post_process left on the device (cp_merge_detections: the class split, soft-nms
         and the max_per_image cut, literal behaviour), then ONE device -> host copy of the table and its counts, from
         which the `results` of run() are cut: the same keys, shapes and bits as merge_outputs gives.  The table stays
-        on the device for device_rows."""
-        rows, C = self.scale_rows, self.num_classes
+        on the device for device_rows.  `rows`: one image's [S, K, ncols] slice of a batch (merge_batch)."""
+        rows, C = self.scale_rows if rows is None else rows, self.num_classes
         S, K, ncols = rows.shape
         self._slot = 0
         lib = _C.lib()

@@ -112,6 +112,9 @@ class opts(object):
         p.add_argument("--no_mask_files", action="store_true",
                        help="with --gt_dir: score in memory and skip the PNG and text output")
         p.add_argument("--not_prefetch_test", action="store_true")
+        p.add_argument("--test_batch_size", type=int, default=1,
+                       help="test.py: images per network launch (detector.run_batch); 1 keeps the per-image loop. "
+                            "Under --keep_res a batch ends where the image size changes; not with --debug > 0")
         p.add_argument("--fix_res", action="store_true")
         p.add_argument("--keep_res", action="store_true")
         # loss
@@ -156,6 +159,11 @@ class opts(object):
         if opt.no_mask_files and not opt.gt_dir:
             self.parser.error("--no_mask_files needs --gt_dir: without a ground truth to score against, the mask files "
                               "are the only result of the evaluation")
+        if opt.test_batch_size < 1:
+            self.parser.error("--test_batch_size must be at least 1 (got %d)" % opt.test_batch_size)
+        if opt.test_batch_size > 1 and opt.debug > 0:
+            self.parser.error("--test_batch_size %d cannot be combined with --debug %d: the debug pictures are drawn "
+                              "per image by run(); use --test_batch_size 1" % (opt.test_batch_size, opt.debug))
         if opt.metric == "ap":
             from .datasets.dataset_factory import dataset_factory
             if not getattr(dataset_factory.get(opt.dataset), "scores_ap", False):

@@ -91,6 +91,40 @@ def warp_affine_normalize(image_u8, trans, mean, std, dst_h, dst_w, flip_copy=Fa
     return out
 
 
+def warp_affine_normalize_batch(image_flat, image_hw, image_offset, trans, mean, std, dst_h, dst_w, flip_copy=False):
+    """warp_affine_normalize for B images of different sizes in one call (cp_preprocess_warp_normalize_batch).
+    image_flat: uint8 1-D HIP tensor, the [H_b,W_b,3] images back to back (`collate_ragged`'s layout); image_hw [B,2],
+    image_offset [B] (bytes) and trans [B,6] or [B,2,3] (forward maps, float64): host arrays or tensors.  Returns fp32
+    [(1 + flip_copy) * B, 3, dst_h, dst_w]: image b at index b, its mirrored copy at B + b, each with the bits
+    warp_affine_normalize gives for that image alone."""
+    import torch
+
+    from .. import _C
+    if not image_flat.is_cuda:
+        raise _C.NativeError("warp_affine_normalize_batch needs HIP device tensors; there is no CPU fallback")
+    if image_flat.dtype != torch.uint8 or image_flat.dim() != 1:
+        raise TypeError("warp_affine_normalize_batch needs a 1-D uint8 image buffer")
+    host = lambda a, dt: np.ascontiguousarray(a.cpu().numpy() if torch.is_tensor(a) else a, dtype=dt)
+    hw = host(image_hw, np.int32).reshape(-1, 2)
+    B = hw.shape[0]
+    off = host(image_offset, np.int64).reshape(B)
+    t = host(trans, np.float64).reshape(B, 6)
+    # the library cannot see the buffer's length: every image must lie inside it
+    if B == 0 or (hw <= 0).any() or (off < 0).any() or \
+            (off + hw[:, 0].astype(np.int64) * hw[:, 1] * 3 > image_flat.numel()).any():
+        raise ValueError("image_offset / image_hw do not describe images inside image_flat (%d bytes)"
+                         % image_flat.numel())
+    m = np.ascontiguousarray(np.asarray(mean, np.float32).ravel()[:3])
+    sd = np.ascontiguousarray(np.asarray(std, np.float32).ravel()[:3])
+    out = torch.empty(((2 if flip_copy else 1) * B, 3, int(dst_h), int(dst_w)), dtype=torch.float32,
+                      device=image_flat.device)
+    P = lambda arr: ctypes.c_void_p(arr.ctypes.data)
+    _C.check(_C.lib().cp_preprocess_warp_normalize_batch(
+        _C.ptr(image_flat), P(off), P(hw), P(t), P(m), P(sd), B, int(dst_h), int(dst_w), 1 if flip_copy else 0,
+        _C.ptr(out), _C.stream()), "cp_preprocess_warp_normalize_batch")
+    return out
+
+
 # ---- host-side helpers of the reference's sampler, kept for API parity (src/lib/utils/image.py) ----
 # The accelerated path builds targets and augments inputs on the device (cp_polydet_targets,
 # cp_preprocess_warp_normalize, cp_color_aug_normalize); these numpy forms serve code that imports the

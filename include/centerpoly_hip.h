@@ -718,6 +718,22 @@ int cp_preprocess_warp_normalize(const uint8_t* src, int32_t src_h, int32_t src_
                                  int32_t dst_h, int32_t dst_w, int32_t flip_copy, float* out,
                                  void* stream);
 
+/* cp_preprocess_warp_normalize_batch: cp_preprocess_warp_normalize for B source images of different sizes in one
+ * launch per 16 images (BaseDetector.run_batch; added without an ABI version change).
+ *   images        DEVICE uint8: the B sources back to back, each [H_b][W_b][3]
+ *   image_offset  HOST int64 [B]: byte offset of image b in `images`      image_hw  HOST int32 [B][2]: (H_b, W_b)
+ *   trans         HOST float64 [B][6]: forward map source -> dst per image       mean, stdv  HOST float32[3]
+ *   out           DEVICE fp32 [(1 + flip_copy) * B][3][dst_h][dst_w], every element written
+ * Image b is at index b of `out`, its horizontally flipped copy (flip_copy != 0) at index B + b: all originals, then
+ * all flips.  Both equal, bit for bit, the two images cp_preprocess_warp_normalize writes for that source and map.
+ * The per-image parameters travel in the kernel arguments (no copy inside the call); `images` must hold every
+ * [offset_b, offset_b + 3 H_b W_b) -- the library cannot see its length.
+ * H_b or W_b > 32767 or dst_h > 65535: CP_EUNSUPPORTED.  Null pointers, batch <= 0, a non-positive size or a negative
+ * offset: CP_EINVAL.  All checks come before any device work. */
+int cp_preprocess_warp_normalize_batch(const uint8_t* images, const int64_t* image_offset, const int32_t* image_hw,
+                                       const double* trans, const float* mean, const float* stdv, int32_t batch,
+                                       int32_t dst_h, int32_t dst_w, int32_t flip_copy, float* out, void* stream);
+
 /* cp_color_aug_normalize: the colour augmentation + normalisation of the TRAINING sampler
  * (src/lib/datasets/sample/polydet.py:128-136: `inp / 255.` -> color_aug -> `(inp - mean) / std`;
  * src/lib/utils/image.py:231-264) in place on the warped input, BGR planes [3][HW] holding x / 255

@@ -34,17 +34,33 @@ def run_test(opt, evaluate=True):
     results = {}
     time_stats = ["tot", "load", "pre", "net", "dec", "post", "merge"]
     avg = {t: AverageMeter() for t in time_stats}
+    from centerpoly_amd.datasets import eval_images
+    batch_size = getattr(opt, "test_batch_size", 1)
+    same_size = not opt.fix_res                      # --keep_res: the network input follows the source size
+
+    def detect(items, images):
+        """One image through run, several through run_batch: the per-image `results` in order; the averages are per
+        image (a batch's times / n)."""
+        if batch_size == 1:
+            ret = detector.run(images[0])
+            per_image, n = [ret["results"]], 1
+        else:
+            ret = detector.run_batch(images)
+            per_image, n = ret["results"], ret["n"]
+        for t in avg:
+            avg[t].update(ret[t] / n, n)
+        return per_image
+
     if opt.dataset == "synthetic":
-        for ind in range(len(dataset)):
-            img = (synth.uniform("test/img%d" % ind, (opt.input_h, opt.input_w, 3)) * 255).astype(np.uint8)
-            ret = detector.run(img)
-            results[ind] = ret["results"]
-            for t in avg:
-                avg[t].update(ret[t])
-            print("[{}/{}] ".format(ind, len(dataset)) + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
+        synthetic = ((ind, (synth.uniform("test/img%d" % ind, (opt.input_h, opt.input_w, 3)) * 255).astype(np.uint8))
+                     for ind in range(len(dataset)))
+        for items in eval_images.group(({"img_id": ind, "image": img} for ind, img in synthetic), batch_size, same_size):
+            for item, res in zip(items, detect(items, [item["image"] for item in items])):
+                results[item["img_id"]] = res
+            print("[{}/{}] ".format(items[-1]["img_id"], len(dataset))
+                  + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
         dataset.run_eval(results, opt.save_dir)
         return {"ap": None, "results": results, "dataset": dataset, "stamps": []}
-    from centerpoly_amd.datasets import eval_images
     evaluator = gt_files = protocol = None
     if getattr(opt, "gt_dir", "") and (getattr(dataset, "scores_ap", False) or getattr(dataset, "ap_protocol", None)):
         from centerpoly_amd.datasets.evaluation import instance_level
@@ -55,16 +71,17 @@ def run_test(opt, evaluate=True):
         evaluator = instance_level.InstanceLevelEvaluator(protocol)
     images = eval_images.EvalImages(dataset, gt_files, protocol)
     stamps = [time.time()]
-    for ind, item in enumerate(eval_images.iterate(images, not opt.not_prefetch_test, opt.num_workers)):
-        ret = detector.run(item["image"])
-        results[item["img_id"]] = ret["results"]
-        if evaluator is not None:
-            dataset.score_instances_device(detector.device_rows(ret["results"]), item["gt_ids"], item["gt_table"],
-                                           evaluator)
-        for t in avg:
-            avg[t].update(ret[t])
+    ind = -1
+    for items in eval_images.group(eval_images.iterate(images, not opt.not_prefetch_test, opt.num_workers), batch_size,
+                                   same_size):
+        for b, (item, res) in enumerate(zip(items, detect(items, [item["image"] for item in items]))):
+            ind += 1
+            results[item["img_id"]] = res
+            if evaluator is not None:
+                dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"], item["gt_table"],
+                                               evaluator)
+            stamps.append(time.time())
         print("[{}/{}] ".format(ind, len(images)) + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
-        stamps.append(time.time())
     if not evaluate:
         ap = None
     elif evaluator is None:
