@@ -136,6 +136,8 @@ _SIGNATURES = {
     "cp_conv_mfma_forward_strided": (c_int32, [_P, _P, c_int32, _P, _P, _P, _P] + [c_int32] * 7 + [_P]),
     "cp_dla_base_pair_supported": (c_int32, [c_int32] * 2),
     "cp_dla_base_pair_forward": (c_int32, [_P] * 6 + [c_int32] * 3 + [_P]),
+    "cp_dla_base_trio_supported": (c_int32, [c_int32] * 2),
+    "cp_dla_base_trio_forward": (c_int32, [_P] * 8 + [c_int32] * 3 + [_P]),
     "cp_conv_mfma_forward_split": (c_int32, [_P, c_int32, _P, _P, _P, _P] + [c_int32] * 9 + [_P]),
     "cp_activation_split": (c_int32, [_P, _P] + [c_int32] * 4 + [_P]),
     "cp_activation_unsplit": (c_int32, [_P, _P] + [c_int32] * 4 + [_P]),
@@ -310,6 +312,14 @@ class KernelTimer(object):
         self.records.setdefault(key, []).append(ev)
         ev[0].record()
         return ev[1]
+
+    def drop(self, key, end):
+        """Forget the pair `start(key)` just opened: the launch was refused, so `end` will never be recorded."""
+        evs = self.records.get(key)
+        if evs and evs[-1][1] is end:
+            evs.pop()
+            if not evs:
+                del self.records[key]
 
     def summary(self):
         torch.cuda.synchronize()

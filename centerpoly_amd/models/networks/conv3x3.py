@@ -380,16 +380,24 @@ def stem_infer(x, conv, w, bias, relu):
     cout, stride = w.shape[0], conv.stride[0]
     if not L.cp_conv7x7_c3_supported(cout, H, W, stride) or B > 65535:
         return None
+    wp = stem_prepared(conv, w)
+    out = torch.empty((B, cout, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=torch.float32, device=x.device)
+    _C.check(L.cp_conv7x7_c3_forward(_C.ptr(x.contiguous()), _C.ptr(wp), _C.ptr(bias), _C.ptr(out), B, H, W, cout,
+                                     stride, 1 if relu else 0, _C.stream()), "cp_conv7x7_c3_forward")
+    return out
+
+
+def stem_prepared(conv, w):
+    """The fragment-order weights of stem_infer for the 7x7 convolution `conv` with the (folded) weight `w`: the same
+    cache slot, so the stem launch and the fused base launch share one prepared buffer."""
+    L = _C.lib()
+    cout = w.shape[0]
 
     def build():
         wp = torch.empty(L.cp_conv7x7_c3_weight_bytes(cout), dtype=torch.uint8, device=w.device)
         _C.check(L.cp_conv7x7_c3_prepare(_C.ptr(w.contiguous()), cout, _C.ptr(wp), _C.stream()), "cp_conv7x7_c3_prepare")
         return wp
-    wp, _ = prepared(conv, "stem", (w,), build)
-    out = torch.empty((B, cout, (H - 1) // stride + 1, (W - 1) // stride + 1), dtype=torch.float32, device=x.device)
-    _C.check(L.cp_conv7x7_c3_forward(_C.ptr(x.contiguous()), _C.ptr(wp), _C.ptr(bias), _C.ptr(out), B, H, W, cout,
-                                     stride, 1 if relu else 0, _C.stream()), "cp_conv7x7_c3_forward")
-    return out
+    return prepared(conv, "stem", (w,), build)[0]
 
 
 def s2_weight_grad(x, weight, go):

@@ -164,12 +164,56 @@ def _base_pair(dla, x):
     (w0, b0), (w1, b1) = dla._folded[1], dla._folded[2]
     x = x.contiguous()
     out = torch.empty((B, 32, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-    end = _C.kernel_timer.start(("conv_base_pair", 16, 32, H, W, B)) if _C.kernel_timer is not None else None
+    key = ("conv_base_pair", 16, 32, H, W, B)
+    end = _C.kernel_timer.start(key) if _C.kernel_timer is not None else None
     rc = L.cp_dla_base_pair_forward(_C.ptr(x), _C.ptr(w0.contiguous()), _C.ptr(b0), _C.ptr(w1.contiguous()), _C.ptr(b1),
                                     _C.ptr(out), B, H, W, _C.stream())
     if rc == -2:
+        if end is not None:
+            _C.kernel_timer.drop(key, end)                  # refused before any launch: no dangling event pair
         return None
     _C.check(rc, "cp_dla_base_pair_forward")
+    if end is not None:
+        end.record()
+    return out
+
+
+# DLA.forward's route for base_layer + level0 + level1 at inference: "auto" -- one launch of cp_dla_base_trio_forward
+# where it applies, "off" -- the stem launch and _base_pair (A/B runs).  The result has the same bits either way.
+BASE_TRIO = "auto"
+
+
+def _base_trio(dla, x):
+    """base_layer + level0 + level1 (folded) as one launch of cp_dla_base_trio_forward -- both 16-channel
+    full-resolution maps stay in LDS; None when the layers / the map are not the kernel's (the caller runs the stem
+    launch and _base_pair)."""
+    cs, c0, c1 = dla.base_layer[0], dla.level0[0], dla.level1[0]
+    if not (BASE_TRIO != "off" and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] == 3
+            and conv3x3.mfma_enabled()
+            and (cs.in_channels, cs.out_channels, cs.kernel_size, cs.stride, cs.padding, cs.dilation, cs.groups,
+                 cs.padding_mode) == (3, 16, (7, 7), (1, 1), (3, 3), (1, 1), 1, "zeros")
+            and (c0.in_channels, c0.out_channels, c0.kernel_size, c0.stride, c0.padding, c0.dilation, c0.groups)
+            == (16, 16, (3, 3), (1, 1), (1, 1), (1, 1), 1)
+            and (c1.in_channels, c1.out_channels, c1.kernel_size, c1.stride, c1.padding, c1.dilation, c1.groups)
+            == (16, 32, (3, 3), (2, 2), (1, 1), (1, 1), 1)):
+        return None
+    B, _, H, W = x.shape
+    L = _C.lib()
+    if not L.cp_dla_base_trio_supported(H, W) or B > 65535:
+        return None
+    (ws, bs), (w0, b0), (w1, b1) = dla._folded
+    wp = conv3x3.stem_prepared(cs, ws)
+    x = x.contiguous()
+    out = torch.empty((B, 32, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+    key = ("conv_base_trio", 3, 32, H, W, B)
+    end = _C.kernel_timer.start(key) if _C.kernel_timer is not None else None
+    rc = L.cp_dla_base_trio_forward(_C.ptr(x), _C.ptr(wp), _C.ptr(bs), _C.ptr(w0.contiguous()), _C.ptr(b0),
+                                    _C.ptr(w1.contiguous()), _C.ptr(b1), _C.ptr(out), B, H, W, _C.stream())
+    if rc == -2:
+        if end is not None:
+            _C.kernel_timer.drop(key, end)                  # refused before any launch: no dangling event pair
+        return None
+    _C.check(rc, "cp_dla_base_trio_forward")
     if end is not None:
         end.record()
     return out
@@ -524,8 +568,11 @@ class DLA(nn.Module):
     def forward(self, x):
         pyramid = []
         if _use_folded(self):
-            x = _conv_folded(x, self.base_layer[0], self._folded[0], relu=True)
-            y1 = _base_pair(self, x) if getattr(self, "skip_level0_output", False) else None
+            skip0 = getattr(self, "skip_level0_output", False)
+            y1 = _base_trio(self, x) if skip0 else None     # the three layers in one launch; same bits as the two below
+            if y1 is None:
+                x = _conv_folded(x, self.base_layer[0], self._folded[0], relu=True)
+                y1 = _base_pair(self, x) if skip0 else None
             if y1 is not None:                      # level0 + level1 in one launch; nobody reads level0's map
                 pyramid += [None, y1]
                 x = y1

@@ -307,6 +307,17 @@ int cp_conv_mfma_forward_strided(const float* const* xs, const int32_t* cs, int3
 int cp_dla_base_pair_supported(int32_t H, int32_t W);
 int cp_dla_base_pair_forward(const float* x, const float* w0, const float* b0, const float* w1, const float* b1, float* out,
                              int32_t B, int32_t H, int32_t W, void* stream);
+/* base_layer + level0 + level1 of the DLA base at inference as ONE launch (added without an ABI version change):
+ *   out = relu(conv3x3 stride 2 pad 1 (relu(conv3x3 pad 1 (relu(conv7x7 pad 3 (image) + stem_bias), w0) + b0), w1) + b1)
+ * image [B][3][H][W] -> out [B][32][(H-1)/2+1][(W-1)/2+1]; stem_wperm is what cp_conv7x7_c3_prepare writes for
+ * Cout = 16; w0, b0, w1, b1 as cp_dla_base_pair_forward; the three biases may be null.  Both 16-channel full-resolution
+ * maps stay in LDS.  The result has the bits of cp_conv7x7_c3_forward (stride 1, ReLU) followed by
+ * cp_dla_base_pair_forward.  W % 4 == 0 and a 16-byte aligned image (cp_dla_base_trio_supported), else
+ * CP_EUNSUPPORTED -- run those two. */
+int cp_dla_base_trio_supported(int32_t H, int32_t W);
+int cp_dla_base_trio_forward(const float* image, const void* stem_wperm, const float* stem_bias, const float* w0,
+                             const float* b0, const float* w1, const float* b1, float* out, int32_t B, int32_t H,
+                             int32_t W, void* stream);
 /* SPLIT activations (round 4; inference, between the two convolutions of a BasicBlock, pose_dla_dcn.py:38-66): a
  * float32 tensor [B][C][H][W] kept as two planes [hi | lo] of [B][C / 8][H][W][8 x bf16] (hi = bf16(v), lo =
  * bf16(v - hi): the halves the convolution's staging forms anyway; same bytes as float32; C % 8 == 0).  The producer's
