@@ -174,8 +174,14 @@ class CityscapesWriterMixin(object):
 
     def class_table(self):
         """cp_writer_instances' table: int32 [C, 2] rows (label id, label has masks) of class 0 .. C-1."""
-        names = self.class_name[1:]
-        return np.array([[self.label_to_id[c], 0 if c in self.no_mask_labels else 1] for c in names], np.int32)
+        return self.writer_class_table()
+
+    @classmethod
+    def writer_class_table(cls):
+        """class_table without an object: the table comes from the class's names and label ids alone (demo.py has no
+        annotation file to construct a data set from)."""
+        names = cls.class_name[1:]
+        return np.array([[cls.label_to_id[c], 0 if c in cls.no_mask_labels else 1] for c in names], np.int32)
 
     def score_instances_device(self, rows_dev, gt_ids, gt_table=None, evaluator=None):
         """One image scored from its detection rows without a pass through host Python: device float32 rows
@@ -355,7 +361,12 @@ class ClassWriterMixin(object):
 
     def class_label_table(self):
         """cp_class_writer_instances' table: int32 [C] label id of class 0 .. C-1."""
-        return np.array([self.label_to_id[c] for c in self.class_name[1:]], np.int32)
+        return self.writer_class_label_table()
+
+    @classmethod
+    def writer_class_label_table(cls):
+        """class_label_table without an object (see CityscapesWriterMixin.writer_class_table)."""
+        return np.array([cls.label_to_id[c] for c in cls.class_name[1:]], np.int32)
 
     def class_masks_device(self, params, canvas, device=None):
         """Masks of instances in drawing order, left on the device: (uint8 [n, H, W], int32 [n] pixel counts)."""

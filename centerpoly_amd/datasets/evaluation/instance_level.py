@@ -43,14 +43,16 @@ class Protocol(object):
       gt_key(dir, file)         key of a ground-truth file below --gt_dir, None for any other file
       image_key(file_name)      the same key from an image's file name
       pred_match(path, key)     whether the text file at `path` (below the result directory) is the image's
-      gt_name(key)              how a missing ground-truth file is named in an error"""
+      gt_name(key)              how a missing ground-truth file is named in an error
+      id_multiplier             an instance id is label * id_multiplier + k (what label_of undoes for an instance)"""
 
     def __init__(self, name, inst_labels, label_ids, void_ids, label_of, gt_filter, gt_key, image_key, pred_match,
-                 gt_name):
+                 gt_name, id_multiplier=1000):
         self.name, self.inst_labels = name, tuple(inst_labels)
         self.label_ids, self.void_ids = tuple(label_ids), tuple(void_ids)
         self.label_of, self.gt_filter, self.gt_key, self.image_key = label_of, gt_filter, gt_key, image_key
         self.pred_match, self.gt_name = pred_match, gt_name
+        self.id_multiplier = id_multiplier
 
 
 def _thousands(ids):
@@ -86,7 +88,8 @@ CITYSCAPES = Protocol("cityscapes", INST_LABELS, LABEL_IDS, VOID_IDS, _thousands
 KITTI = Protocol("kitti", INST_LABELS, LABEL_IDS, VOID_IDS, lambda ids: ids // 256, _every,
                  lambda root, f: f[:-4] if f.endswith(".png") else None,
                  lambda file_name: os.path.splitext(os.path.basename(file_name))[0],
-                 lambda path, key: os.path.basename(path) == key + ".txt", lambda key: key + ".png")
+                 lambda path, key: os.path.basename(path) == key + ".txt", lambda key: key + ".png",
+                 id_multiplier=256)
 # IDDscripts: the anue label table (levels of 1000 as in Cityscapes); instances2dict lets an id in only when it is
 # not 255 and its thousands are a label between 6 and 18, so there are no group ids in its tables
 IDD = Protocol("IDD", ("person", "rider", "motorcycle", "bicycle", "autorickshaw", "car", "truck", "bus",

@@ -82,6 +82,7 @@ class BaseDetector(object):
         self.opt = opt
         self.pause = True
         self.debugger = None                                 # made at the first run() with --debug >= 1, then kept
+        self.image_sizes = []                                # (width, height) per image of the last run() / run_batch()
 
     def _input_geometry(self, height, width, scale):
         """(new_height, new_width, inp_height, inp_width, c, s, trans_input) of an image of height x width at a test
@@ -219,6 +220,7 @@ class BaseDetector(object):
             pre_processed = True
         loaded_time = time.time()
         load_time += loaded_time - start_time
+        self.image_sizes = [(int(image.shape[1]), int(image.shape[0]))]    # (width, height): the default canvas
 
         detections = []
         for scale in self.scales:
@@ -286,6 +288,7 @@ class BaseDetector(object):
             if not isinstance(im, np.ndarray):
                 raise TypeError("run_batch takes 8-bit [H,W,3] arrays or paths (got %s)" % type(im).__name__)
         loaded_time = time.time()
+        self.image_sizes = [(int(im.shape[1]), int(im.shape[0])) for im in images]
         detections = []
         for scale in self.scales:
             scale_start_time = time.time()

@@ -154,6 +154,23 @@ class PolydetDetector(BaseDetector):
                 for j, r in sorted(results.items())]
         return np.ascontiguousarray(np.concatenate(rows, axis=0), np.float32)
 
+    def instances(self, results=None, image=0, thresh=None, canvas=None):
+        """The instance maps (detectors/instances.py: who owns each pixel, id and label images, masks, the table) of
+        image `image` of the last run() / run_batch(), drawn by the writer of --dataset on `canvas` (width, height; by
+        default the size of that image) with the detections above `thresh` (by default --thresh).  Works on
+        device_rows, so after several test scales or --nms as well."""
+        from ..datasets.dataset_factory import dataset_factory
+        from .instances import instance_maps
+        rows = self.device_rows(results, image)
+        if canvas is None:
+            if not 0 <= image < len(self.image_sizes):
+                raise IndexError("image %d: the last call held %d images" % (image, len(self.image_sizes)))
+            canvas = self.image_sizes[image]
+        if self.opt.dataset not in dataset_factory:
+            raise KeyError("dataset %r is not registered (have: %s)" % (self.opt.dataset, sorted(dataset_factory)))
+        return instance_maps(rows, dataset_factory[self.opt.dataset], canvas,
+                             self.opt.thresh if thresh is None else thresh)
+
     def debug(self, debugger, images, dets, output, scale=1):
         """pred_hm_<scale>: the class heat maps over the network input; out_pred_<scale>: the network input with
         the boxes of the centres above --center_thresh, in network-input coordinates (reference :78-91)."""

@@ -111,6 +111,13 @@ class opts(object):
                             "run_eval scores the masks on the GPU (Cityscapes instance-level AP); empty: files only")
         p.add_argument("--no_mask_files", action="store_true",
                        help="with --gt_dir: score in memory and skip the PNG and text output")
+        p.add_argument("--save_ids", action="store_true",
+                       help="demo.py / test.py: per image <stem>_instanceIds.png (16 bit), <stem>_labelIds.png (8 bit) "
+                            "and <stem>.json (the live instances) under <save_dir>/instances/, from the detections "
+                            "above --thresh (detector.instances)")
+        p.add_argument("--save_masks", action="store_true",
+                       help="demo.py / test.py: per image <stem>.txt and masks/<stem>_<k>.png under "
+                            "<save_dir>/instances/, the Cityscapes result layout for every data set")
         p.add_argument("--not_prefetch_test", action="store_true")
         p.add_argument("--test_batch_size", type=int, default=1,
                        help="test.py: images per network launch (detector.run_batch); 1 keeps the per-image loop. "

@@ -4,6 +4,9 @@
 detector with --debug >= 1: the detections are drawn on the GPU and written as `<stem>_polydet.png` into the
 experiment's debug directory (--debug 2 adds the heat-map view and the centre boxes).  One timing line per image, as
 the reference prints it, with the time of the pictures appended.  `--load_model ''` runs the random initialisation.
+--save_ids / --save_masks also write every image's instance maps (detector.instances, drawn by the writer of --dataset
+on the image's own canvas from the detections above --thresh) under `<save_dir>/instances/`: `<stem>_instanceIds.png`,
+`<stem>_labelIds.png` and `<stem>.json`; `<stem>.txt` and `masks/<stem>_<k>.png`.
 There is no video decoder here: `webcam` and video files are refused."""
 import os
 import sys
@@ -47,6 +50,14 @@ def demo(opt):
         ret = detector.run(name)
         print("".join("{} {:.3f}s |".format(stat, ret[stat]) for stat in time_stats)
               + "vis {:.3f}s |".format(ret["vis_time"]))
+        if opt.save_ids or opt.save_masks:
+            from centerpoly_amd.detectors import instances
+            maps = detector.instances(ret["results"])
+            inst_dir, stem = os.path.join(opt.save_dir, "instances"), instances.image_stem(name)
+            if opt.save_ids:
+                instances.save_ids(maps, inst_dir, stem)
+            if opt.save_masks:
+                instances.save_masks(maps, inst_dir, stem)
         out.append((name, ret))
     return out
 

@@ -54,7 +54,7 @@ extern "C" {
                               cp_class_instance_masks, cp_class_writer_instances, cp_render_overlay_workspace_bytes,
                               cp_render_overlay, cp_render_heatmap, cp_soft_nms_device, cp_merge_detections(_workspace_bytes),
                               cp_dcn_v2_forward_slices(_count), cp_dcn_splitk_reduce, cp_depthwise_up_forward_slices,
-                              cp_conv1x1_stream_*, cp_conv3x3_stream_* */
+                              cp_conv1x1_stream_*, cp_conv3x3_stream_*, cp_instance_map(_workspace_bytes) */
 
 enum {
   CP_OK = 0,
@@ -559,6 +559,45 @@ int cp_class_writer_instances(const float* rows, int32_t R, int32_t N, float thr
                               const int32_t* class_label, int32_t C, int32_t* n_out, int32_t* src, int32_t* poly,
                               int32_t* group, uint8_t* flags, int32_t* label, float* conf, int32_t* text_index,
                               void* stream);
+
+/* ------------------------------------------------ instance maps (detectors/instances.py) --
+ * cp_instance_map: the masks of ONE image merged, depth resolved, into one map with its per-instance tables -- which
+ * instance owns each pixel, the `*_instanceIds.png` / `*_labelIds.png` values, and what every instance shows.
+ *   masks  DEVICE uint8 [n][H][W], non-zero = inside (what cp_instance_masks and cp_class_instance_masks leave)
+ *   flags  DEVICE uint8 [n]                      counts DEVICE int32 [n] or NULL
+ *   label  DEVICE int32 [n]                      prio   DEVICE fp32 [n] or NULL
+ *   bounds DEVICE int32 [n][4] inclusive x0, y0, x1, y1, or NULL
+ * With
+ *   live(i)      (flags[i] & flag_mask) != 0 and (counts NULL or counts[i] > min_count)
+ *   covers(i, p) live(i), p inside bounds[i] clipped to the canvas (NULL bounds: the whole canvas; x1 < x0 or y1 < y0:
+ *                nothing) and masks[i][p] != 0.  Pixels of a mask outside its bounds are ignored, in every code path
+ *                alike: bounds tighter than the mask give a defined result
+ *   before(i, j) NULL prio: i < j; otherwise prio[i] < prio[j], or equal and i < j; a NaN sorts after every number,
+ *                NaNs among themselves by index
+ *   winner(p)    the covering instance that is `before` every other covering instance
+ * the outputs are
+ *   index   DEVICE uint8 [H][W]: winner(p), 255 where nothing covers
+ *   value   DEVICE int32 [n]: label[i] * multiplier + k for a live instance, k the number of live j < i with
+ *           label[j] == label[i]; -1 for a dead one
+ *   ids     DEVICE int32 [H][W] or NULL (not written): value[winner(p)], `background` where nothing covers
+ *   labels  DEVICE int32 [H][W] or NULL (not written): label[winner(p)], `background` where nothing covers
+ *   visible DEVICE int32 [n]: pixels instance i wins
+ *   box     DEVICE int32 [n][4]: inclusive min x, min y, max x, max y of the pixels it wins; {W, H, -1, -1} when it
+ *           wins none or is dead
+ * 0 <= n <= 128, H * W < 2^31 (CP_EUNSUPPORTED beyond); H, W >= 1, multiplier >= 1, the required pointers (index
+ * always, masks, flags, label, value, visible and box when n > 0) otherwise CP_EINVAL; workspace:
+ * cp_instance_map_workspace_bytes (the tables in rank order), shorter: CP_EWORKSPACE.  All checks come before any device
+ * work.  n == 0 fills the maps and reads no mask.  Any H, W and any alignment of masks (a 16-pixel piece of a row
+ * that lies on a 16-byte boundary takes the wide loads and stores: every full piece when the planes are 16-byte
+ * aligned and W % 16 == 0).  A workgroup owns a tile of 16 x 256 pixels and reads a plane only where its clipped
+ * bounds meet the tile and pixels are still undecided.  Two launches whatever n is; integer results, the same bits
+ * on every run. */
+size_t cp_instance_map_workspace_bytes(int32_t n, int32_t H, int32_t W);
+int cp_instance_map(const uint8_t* masks, int32_t n, int32_t H, int32_t W, const uint8_t* flags, int32_t flag_mask,
+                    const int32_t* counts, int32_t min_count, const int32_t* label, const float* prio,
+                    const int32_t* bounds, int32_t multiplier, int32_t background, uint8_t* index, int32_t* ids,
+                    int32_t* labels, int32_t* value, int32_t* visible, int32_t* box, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------ training annotations (make_annotations.py) --
  * The "regular interval" recipe of the reference's offline annotation tools (KITTIPolyStuff/Tools/

@@ -4,8 +4,9 @@
 image files (`dataset.images` -> `coco.loadImgs` -> `read_image`), by default through a prefetching DataLoader whose
 workers decode ahead of the detector, with --not_prefetch_test in a plain loop.  With --gt_dir every image is scored on
 the device as it passes (score_instances_device of the data set's writer: Cityscapes, or KITTI / IDD by their own
-evaluators' protocols) and the instance-level allAp is returned.  `--dataset synthetic` feeds hash-generated uint8
-arrays (no files)."""
+evaluators' protocols) and the instance-level allAp is returned.  With --save_ids / --save_masks every image's
+instance maps (detector.instances: id and label images, the table, the masks) are written under
+`<save_dir>/instances/` as it passes.  `--dataset synthetic` feeds hash-generated uint8 arrays (no files)."""
 import os
 import sys
 import time
@@ -51,8 +52,24 @@ def run_test(opt, evaluate=True):
             avg[t].update(ret[t] / n, n)
         return per_image
 
+    save_ids, save_masks = getattr(opt, "save_ids", False), getattr(opt, "save_masks", False)
+    inst_dir = os.path.join(opt.save_dir, "instances")
+
+    def save_instances(file_name, res, b):
+        """--save_ids / --save_masks: the instance maps of image b of the last launch, on its own canvas."""
+        from centerpoly_amd.detectors import instances
+        maps = detector.instances(res, image=b)
+        stem = instances.image_stem(file_name)
+        if save_ids:
+            instances.save_ids(maps, inst_dir, stem)
+        if save_masks:
+            instances.save_masks(maps, inst_dir, stem)
+
     if opt.dataset == "synthetic":
-        synthetic = ((ind, (synth.uniform("test/img%d" % ind, (opt.input_h, opt.input_w, 3)) * 255).astype(np.uint8))
+        if save_ids or save_masks:
+            raise ValueError("--save_ids / --save_masks draw with a data set's result writer; the synthetic set has "
+                             "none (use cityscapes, kitti_poly or IDD)")
+        synthetic =((ind, (synth.uniform("test/img%d" % ind, (opt.input_h, opt.input_w, 3)) * 255).astype(np.uint8))
                      for ind in range(len(dataset)))
         for items in eval_images.group(({"img_id": ind, "image": img} for ind, img in synthetic), batch_size, same_size):
             for item, res in zip(items, detect(items, [item["image"] for item in items])):
@@ -80,6 +97,8 @@ def run_test(opt, evaluate=True):
             if evaluator is not None:
                 dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"], item["gt_table"],
                                                evaluator)
+            if save_ids or save_masks:
+                save_instances(dataset.coco.loadImgs(ids=[item["img_id"]])[0]["file_name"], res, b)
             stamps.append(time.time())
         print("[{}/{}] ".format(ind, len(images)) + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
     if not evaluate:
