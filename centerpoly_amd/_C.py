@@ -111,6 +111,8 @@ _SIGNATURES = {
     "cp_instance_map_workspace_bytes": (c_size_t, [c_int32] * 3),
     "cp_instance_map": (c_int32, [_P, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32,
                                   _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "cp_pixel_confusion_workspace_bytes": (c_size_t, [c_int32]),
+    "cp_pixel_confusion": (c_int32, [_P, _P, _P] + [c_int32] * 5 + [_P, _P, c_int32, _P, _P, _P, _P, c_size_t, _P]),
     "cp_polydet_post_process": (c_int32, [_P, _P, c_float, c_int32, c_int32, c_int32, _P, _P]),
     "cp_polydet_targets_workspace_bytes": (c_size_t, [POINTER(TargetShape)]),
     "cp_polydet_targets": (c_int32, [POINTER(TargetShape)] + [_P] * 19 + [_P, c_size_t, _P]),

@@ -118,6 +118,10 @@ class opts(object):
         p.add_argument("--save_masks", action="store_true",
                        help="demo.py / test.py: per image <stem>.txt and masks/<stem>_<k>.png under "
                             "<save_dir>/instances/, the Cityscapes result layout for every data set")
+        p.add_argument("--pixel_iou", action="store_true",
+                       help="test.py: also score every image's label map (detector.instances) at pixel level on the "
+                            "GPU: class and category IoU and instance-weighted iIoU, the confusion matrix; needs "
+                            "--gt_dir; cityscapes and kitti_poly")
         p.add_argument("--not_prefetch_test", action="store_true")
         p.add_argument("--test_batch_size", type=int, default=1,
                        help="test.py: images per network launch (detector.run_batch); 1 keeps the per-image loop. "
@@ -166,6 +170,15 @@ class opts(object):
         if opt.no_mask_files and not opt.gt_dir:
             self.parser.error("--no_mask_files needs --gt_dir: without a ground truth to score against, the mask files "
                               "are the only result of the evaluation")
+        if opt.pixel_iou:
+            from .datasets.evaluation import pixel_level
+            if opt.dataset not in pixel_level.DATASET_PROTOCOL:
+                self.parser.error("--pixel_iou scores %s only; dataset %r is refused: %s"
+                                  % (" and ".join(sorted(pixel_level.DATASET_PROTOCOL)), opt.dataset,
+                                     pixel_level.REFUSED.get(opt.dataset, "it has no pixel-level protocol here")))
+            if not opt.gt_dir:
+                self.parser.error("--pixel_iou needs --gt_dir: the label maps are scored against the instance-id "
+                                  "ground truth found there")
         if opt.test_batch_size < 1:
             self.parser.error("--test_batch_size must be at least 1 (got %d)" % opt.test_batch_size)
         if opt.test_batch_size > 1 and opt.debug > 0:

@@ -54,7 +54,8 @@ extern "C" {
                               cp_class_instance_masks, cp_class_writer_instances, cp_render_overlay_workspace_bytes,
                               cp_render_overlay, cp_render_heatmap, cp_soft_nms_device, cp_merge_detections(_workspace_bytes),
                               cp_dcn_v2_forward_slices(_count), cp_dcn_splitk_reduce, cp_depthwise_up_forward_slices,
-                              cp_conv1x1_stream_*, cp_conv3x3_stream_*, cp_instance_map(_workspace_bytes) */
+                              cp_conv1x1_stream_*, cp_conv3x3_stream_*, cp_instance_map(_workspace_bytes),
+                              cp_pixel_confusion(_workspace_bytes) */
 
 enum {
   CP_OK = 0,
@@ -598,6 +599,42 @@ int cp_instance_map(const uint8_t* masks, int32_t n, int32_t H, int32_t W, const
                     const int32_t* bounds, int32_t multiplier, int32_t background, uint8_t* index, int32_t* ids,
                     int32_t* labels, int32_t* value, int32_t* visible, int32_t* box, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------ pixel-level evaluation --
+ * cp_pixel_confusion: the pixel counting of evalPixelLevelSemanticLabeling (cityscapesscripts, kittiscripts) for ONE
+ * image -- the confusion matrix (addToConfusionMatrix.cEvaluatePair) and the per-instance counts of the
+ * instance-weighted iIoU -- from an 8-bit prediction and the 16-bit instance-id image.
+ *   pred        DEVICE uint8 [H][W]                   pred_label  HOST uint8 [256]: label of a prediction byte
+ *   gt_ids      DEVICE uint16 [H][W]                  label_group HOST int8 [L]: group of a label, -1 (negative) = none
+ *   inst_ids    DEVICE int32 [G], distinct (values outside 16 bits match no pixel)
+ *   conf        DEVICE int64 [L][L], ADDED to         inst        DEVICE int32 [G][3], written (zeroed by the call)
+ *   bad         DEVICE int32 [2], ADDED to
+ * Definitions:
+ *   * For pixel x with v = gt_ids[x], the ground-truth label is g = v < id_direct_below ? v : v / id_divisor.
+ *       Cityscapes: id_direct_below = 1000, id_divisor = 1000.    KITTI: id_direct_below = 0, id_divisor = 256.
+ *   * The predicted label is p = pred_label[pred[x]].
+ *   * g >= L: bad[0] += 1 and the pixel is counted nowhere else (in neither conf nor bad[1]).
+ *   * Otherwise p >= L: bad[1] += 1 and the pixel is counted nowhere else.
+ *   * Otherwise conf[g][p] += 1.
+ *   * For column j with id = inst_ids[j] and gl its label by the rule above:
+ *       inst[j][0] = pixels with v == id.
+ *       inst[j][1] = of those, pixels with p == gl.
+ *       inst[j][2] = of those, pixels with label_group[p] == label_group[gl] and label_group[gl] >= 0.
+ *       Pixels with a bad p count in inst[j][0] only; so do all pixels of a column with gl >= L.
+ *   * Ids not in inst_ids touch no instance column.
+ *   * inst is zeroed by the call.  conf and bad are not, so a run keeps its matrix on the device and reads it once at
+ *     the end.
+ * Limits: 1 <= L <= 64, 0 <= G <= 1024 (with G == 0, inst and inst_ids may be NULL), H * W < 2^31; beyond the upper
+ * limits CP_EUNSUPPORTED.  Null pointers, non-positive sizes, id_divisor < 1, id_direct_below < 0: CP_EINVAL.
+ * workspace: cp_pixel_confusion_workspace_bytes (the id and prediction tables), shorter: CP_EWORKSPACE.  All checks
+ * come before any device work.  Any H, any W, any alignment of pred and gt_ids (a 16-byte aligned image takes 16-byte
+ * loads for its full pieces of 16 pixels, each image by itself).  Two launches whatever G is; the counters live in
+ * LDS as 32-bit words, which H * W < 2^31 cannot overflow.  Integer results, the same bits on every run. */
+size_t cp_pixel_confusion_workspace_bytes(int32_t G);
+int cp_pixel_confusion(const uint8_t* pred, const uint8_t* pred_label, const uint16_t* gt_ids, int32_t H, int32_t W,
+                       int32_t id_divisor, int32_t id_direct_below, int32_t L, const int8_t* label_group,
+                       const int32_t* inst_ids, int32_t G, int64_t* conf, int32_t* inst, int32_t* bad,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------ training annotations (make_annotations.py) --
  * The "regular interval" recipe of the reference's offline annotation tools (KITTIPolyStuff/Tools/

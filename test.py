@@ -6,7 +6,10 @@ workers decode ahead of the detector, with --not_prefetch_test in a plain loop. 
 the device as it passes (score_instances_device of the data set's writer: Cityscapes, or KITTI / IDD by their own
 evaluators' protocols) and the instance-level allAp is returned.  With --save_ids / --save_masks every image's
 instance maps (detector.instances: id and label images, the table, the masks) are written under
-`<save_dir>/instances/` as it passes.  `--dataset synthetic` feeds hash-generated uint8 arrays (no files)."""
+`<save_dir>/instances/` as it passes.  With --pixel_iou (and --gt_dir) the same maps are also scored at pixel level on
+the device (evaluation/pixel_level.py): the class and category tables follow the AP table,
+resultPixelLevelSemanticLabeling.json is written to save_dir and run_test's dict gains "pixel".  `--dataset synthetic`
+feeds hash-generated uint8 arrays (no files)."""
 import os
 import sys
 import time
@@ -26,7 +29,8 @@ from centerpoly_amd.utils.utils import AverageMeter
 def run_test(opt, evaluate=True):
     """One pass over the validation images: {"ap": run_eval's return value (None for the synthetic set),
     "results": {image id: {class: rows}}, "dataset": the data set object (its last_evaluator holds the count
-    tables of a scored run), "stamps": the clock before the first image and after every image}.  evaluate=False
+    tables of a scored run), "stamps": the clock before the first image and after every image, and with --pixel_iou
+    "pixel": the pixel-level result dictionary}.  evaluate=False
     stops after the image loop (tools/probe_eval_tail.py times the loop without run_eval's files)."""
     Dataset = get_dataset(opt.dataset, opt.task)
     opt = opts().update_dataset_info_and_set_heads(opt, Dataset)
@@ -55,10 +59,9 @@ def run_test(opt, evaluate=True):
     save_ids, save_masks = getattr(opt, "save_ids", False), getattr(opt, "save_masks", False)
     inst_dir = os.path.join(opt.save_dir, "instances")
 
-    def save_instances(file_name, res, b):
-        """--save_ids / --save_masks: the instance maps of image b of the last launch, on its own canvas."""
+    def save_instances(file_name, maps):
+        """--save_ids / --save_masks: the instance maps of one image, on its own canvas."""
         from centerpoly_amd.detectors import instances
-        maps = detector.instances(res, image=b)
         stem = instances.image_stem(file_name)
         if save_ids:
             instances.save_ids(maps, inst_dir, stem)
@@ -86,6 +89,13 @@ def run_test(opt, evaluate=True):
         protocol = instance_level.PROTOCOLS[getattr(dataset, "ap_protocol", None) or "cityscapes"]
         gt_files = instance_level.find_gt_files(opt.gt_dir, protocol)
         evaluator = instance_level.InstanceLevelEvaluator(protocol)
+    pixel = None
+    if getattr(opt, "pixel_iou", False):
+        from centerpoly_amd.datasets.evaluation import pixel_level
+        if evaluator is None:
+            raise ValueError("--pixel_iou needs --gt_dir and a data set with a pixel-level protocol (cityscapes, "
+                             "kitti_poly)")
+        pixel = pixel_level.PixelLevelEvaluator(pixel_level.PROTOCOLS[pixel_level.DATASET_PROTOCOL[opt.dataset]])
     images = eval_images.EvalImages(dataset, gt_files, protocol)
     stamps = [time.time()]
     ind = -1
@@ -97,8 +107,13 @@ def run_test(opt, evaluate=True):
             if evaluator is not None:
                 dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"], item["gt_table"],
                                                evaluator)
-            if save_ids or save_masks:
-                save_instances(dataset.coco.loadImgs(ids=[item["img_id"]])[0]["file_name"], res, b)
+            if save_ids or save_masks or pixel is not None:
+                file_name = dataset.coco.loadImgs(ids=[item["img_id"]])[0]["file_name"]
+                maps = detector.instances(res, image=b)                    # once for the files and the score
+                if save_ids or save_masks:
+                    save_instances(file_name, maps)
+                if pixel is not None:
+                    pixel.add_maps(maps, item["gt_ids"], file_name)
             stamps.append(time.time())
         print("[{}/{}] ".format(ind, len(images)) + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
     if not evaluate:
@@ -107,7 +122,12 @@ def run_test(opt, evaluate=True):
         ap = dataset.run_eval(results, opt.save_dir)
     else:
         ap = dataset.finish_scored_eval(results, opt.save_dir, evaluator)
-    return {"ap": ap, "results": results, "dataset": dataset, "stamps": stamps}
+    out = {"ap": ap, "results": results, "dataset": dataset, "stamps": stamps}
+    if pixel is not None and evaluate:
+        out["pixel"] = pixel.summarize()
+        print(pixel_level.format_results(out["pixel"], pixel.protocol))
+        pixel_level.write_results(out["pixel"], opt.save_dir)
+    return out
 
 
 def test(opt):
