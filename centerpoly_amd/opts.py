@@ -122,6 +122,14 @@ class opts(object):
                        help="test.py: also score every image's label map (detector.instances) at pixel level on the "
                             "GPU: class and category IoU and instance-weighted iIoU, the confusion matrix; needs "
                             "--gt_dir; cityscapes and kitti_poly")
+        p.add_argument("--panoptic", action="store_true",
+                       help="test.py: also score every image's instance map (detector.instances) as a panoptic "
+                            "segmentation on the GPU: PQ / SQ / RQ per class and for All / Things / Stuff; needs "
+                            "--gt_dir; cityscapes only")
+        p.add_argument("--save_panoptic", action="store_true",
+                       help="demo.py / test.py: per image <stem>_panoptic.png and one cityscapes_panoptic_val.json in "
+                            "COCO panoptic format under <save_dir>/panoptic/, from the detections above --thresh; "
+                            "cityscapes only")
         p.add_argument("--not_prefetch_test", action="store_true")
         p.add_argument("--test_batch_size", type=int, default=1,
                        help="test.py: images per network launch (detector.run_batch); 1 keeps the per-image loop. "
@@ -179,6 +187,22 @@ class opts(object):
             if not opt.gt_dir:
                 self.parser.error("--pixel_iou needs --gt_dir: the label maps are scored against the instance-id "
                                   "ground truth found there")
+        if opt.panoptic:
+            from .datasets.evaluation import panoptic
+            if opt.dataset not in panoptic.DATASETS:
+                self.parser.error("--panoptic scores %s only; dataset %r is refused: %s"
+                                  % (" and ".join(panoptic.DATASETS), opt.dataset,
+                                     panoptic.REFUSED.get(opt.dataset, "it has no panoptic protocol here")))
+            if not opt.gt_dir:
+                self.parser.error("--panoptic needs --gt_dir: the instance maps are scored against the instance-id "
+                                  "ground truth found there")
+        if opt.save_panoptic and opt.dataset != "cityscapes":
+            self.parser.error("--save_panoptic writes %s only; dataset %r is refused: %s"
+                              % ("cityscapes", opt.dataset,
+                                 "the synthetic set has no result writer to draw instance maps with"
+                                 if opt.dataset == "synthetic" else
+                                 "cityscapes_panoptic_<split>.json is the Cityscapes format and carries Cityscapes label "
+                                 "ids, which this data set's instances do not have"))
         if opt.test_batch_size < 1:
             self.parser.error("--test_batch_size must be at least 1 (got %d)" % opt.test_batch_size)
         if opt.test_batch_size > 1 and opt.debug > 0:

@@ -46,6 +46,7 @@ def demo(opt):
     opt = opts().update_dataset_info_and_set_heads(opt, dataset_factory[opt.dataset])
     detector = detector_factory[opt.task](opt)
     out = []
+    pan_entries = []
     for name in names:
         ret = detector.run(name)
         print("".join("{} {:.3f}s |".format(stat, ret[stat]) for stat in time_stats)
@@ -58,7 +59,15 @@ def demo(opt):
                 instances.save_ids(maps, inst_dir, stem)
             if opt.save_masks:
                 instances.save_masks(maps, inst_dir, stem)
+        if getattr(opt, "save_panoptic", False):
+            from centerpoly_amd.datasets.evaluation import panoptic
+            from centerpoly_amd.detectors import instances
+            pan_dir = os.path.join(opt.save_dir, "panoptic")
+            pan_entries.append(panoptic.save_panoptic(detector.instances(ret["results"]), pan_dir,
+                                                      instances.image_stem(name)))
         out.append((name, ret))
+    if pan_entries:
+        panoptic.write_panoptic_json(pan_dir, pan_entries)
     return out
 
 

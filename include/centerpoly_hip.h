@@ -55,7 +55,7 @@ extern "C" {
                               cp_render_overlay, cp_render_heatmap, cp_soft_nms_device, cp_merge_detections(_workspace_bytes),
                               cp_dcn_v2_forward_slices(_count), cp_dcn_splitk_reduce, cp_depthwise_up_forward_slices,
                               cp_conv1x1_stream_*, cp_conv3x3_stream_*, cp_instance_map(_workspace_bytes),
-                              cp_pixel_confusion(_workspace_bytes) */
+                              cp_pixel_confusion(_workspace_bytes), cp_panoptic_pairs(_workspace_bytes), cp_panoptic_match */
 
 enum {
   CP_OK = 0,
@@ -635,6 +635,57 @@ int cp_pixel_confusion(const uint8_t* pred, const uint8_t* pred_label, const uin
                        int32_t id_divisor, int32_t id_direct_below, int32_t L, const int8_t* label_group,
                        const int32_t* inst_ids, int32_t G, int64_t* conf, int32_t* inst, int32_t* bad,
                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------ panoptic quality --
+ * The protocol of evalPanopticSemanticLabeling (pq_compute_single_core) for ONE image, with the ground-truth segments
+ * that createPanopticImgs derives from the 16-bit instance-id image, counted and matched on the device: nothing comes
+ * back to the host per image.
+ *
+ * cp_panoptic_pairs: the segments of the ground truth and the pixel count of every (segment, prediction) pair.
+ *   index       DEVICE uint8 [H][W]: what cp_instance_map writes     n  number of slots, 0 .. 255
+ *   gt_ids      DEVICE uint16 [H][W]                                  id_divisor, id_direct_below: as cp_pixel_confusion
+ *   label_flags HOST uint8 [L]: bit 0 = evaluated (not ignoreInEval), bit 1 = has instances
+ *   seg         DEVICE int32 [1025][4] out, 16-byte aligned      pairs  DEVICE int32 [1025][n + 1] out
+ *   - the label of a value v is g = v < id_direct_below ? v : v / id_divisor; the pixel is VOID (row 0) when g >= L or
+ *     label g is not evaluated, otherwise it belongs to the segment of value v.  The image's segments are its distinct
+ *     non-void values, ascending: rows 1 .. G.  A segment is crowd when v < id_direct_below and its label has
+ *     instances.  The column of a pixel is index[x] when that is < n, else n ("no prediction": 255 and anything >= n).
+ *   - seg[0] = {G, void pixels, 0, 0}, seg[r] = {value, label, crowd, area}; pairs[r][c] = pixels in row r and column c.
+ *     Both are fully written for rows 0 .. min(G, 1024) (pairs is zeroed whole).  With G > 1024, seg[0][0] holds the
+ *     true G, the tables hold the first 1024 segments and the pixels of the others are counted nowhere.
+ * Limits: 1 <= L <= 64, 0 <= n <= 255, H * W < 2^31; beyond the upper limits CP_EUNSUPPORTED.  Null pointers,
+ * non-positive sizes, n < 0, id_divisor < 1, id_direct_below < 0, a misaligned table: CP_EINVAL.  workspace:
+ * cp_panoptic_pairs_workspace_bytes (the presence bytes and the id -> row table, 16-byte aligned), shorter:
+ * CP_EWORKSPACE.  All checks come before any device work.  Any H, any W, any alignment of index and gt_ids (a 16-byte
+ * aligned image takes 16-byte loads for its full pieces of 16 pixels, each image by itself).  Five launches whatever
+ * the content; the segments are found on the device (presence pass, then a compaction of the 65536 entries).  The
+ * counting keeps a workgroup's table in LDS when (min(G, 1024) + 1) * (n + 1) <= 15360 cells and adds to the global
+ * table directly otherwise.  Integer atomics only: the same bits on every run.
+ *
+ * cp_panoptic_match: the matching on those two tables, one launch of one workgroup.
+ *   pred_label  HOST int32 [n]: label of a slot                      label_flags as above
+ *   stat        DEVICE int64 [L][3] = tp, fp, fn, ADDED to           iou  DEVICE float64 [L], ADDED to
+ *   bad         DEVICE int32 [2], ADDED to                           match DEVICE int32 [n] out, or NULL
+ *   - area_p[i] = sum over r of pairs[r][i], area_g[r] = seg[r][3].  Slot i is a predicted segment when area_p[i] > 0
+ *     and pred_label[i] is in [0, L) and evaluated; a slot with pixels but another label counts bad[1] += 1 and is
+ *     absent (the evaluator raises a KeyError there).
+ *   - (r, i) match when r >= 1, row r is not crowd, seg[r][1] == pred_label[i] and 2 * inter > union with
+ *     inter = pairs[r][i], union = area_g[r] + area_p[i] - inter - pairs[0][i] (an integer comparison that decides as
+ *     the evaluator's float64 inter / union > 0.5 for counts below 2^32).  A match counts tp[label] += 1 and
+ *     iou[label] += (double)inter / (double)union; the additions of one image happen in ascending row order, each onto
+ *     the running value, so the sum is the evaluator's sequence of operations and the same bits on every run.
+ *   - every non-crowd row without a match: fn[label] += 1.  Every existing slot without a match: with
+ *     x = pairs[0][i] + pairs[rc][i], rc the crowd row of the slot's label (the one of highest value if several),
+ *     the slot is ignored if 2 * x > area_p[i], otherwise fp[label] += 1.
+ *   - match[i] = the matched row, 0 for an existing unmatched slot, -1 for an absent one.
+ *   - seg[0][0] > 1024: bad[0] += 1, match is all -1 and nothing else is added for the image.
+ * Limits and codes as above; stat and iou 8-byte aligned. */
+size_t cp_panoptic_pairs_workspace_bytes(void);
+int cp_panoptic_pairs(const uint8_t* index, int32_t n, const uint16_t* gt_ids, int32_t H, int32_t W, int32_t id_divisor,
+                      int32_t id_direct_below, int32_t L, const uint8_t* label_flags, int32_t* seg, int32_t* pairs,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int cp_panoptic_match(const int32_t* seg, const int32_t* pairs, int32_t n, const int32_t* pred_label, int32_t L,
+                      const uint8_t* label_flags, int64_t* stat, double* iou, int32_t* bad, int32_t* match, void* stream);
 
 /* ------------------------------------------------ training annotations (make_annotations.py) --
  * The "regular interval" recipe of the reference's offline annotation tools (KITTIPolyStuff/Tools/

@@ -8,7 +8,10 @@ evaluators' protocols) and the instance-level allAp is returned.  With --save_id
 instance maps (detector.instances: id and label images, the table, the masks) are written under
 `<save_dir>/instances/` as it passes.  With --pixel_iou (and --gt_dir) the same maps are also scored at pixel level on
 the device (evaluation/pixel_level.py): the class and category tables follow the AP table,
-resultPixelLevelSemanticLabeling.json is written to save_dir and run_test's dict gains "pixel".  `--dataset synthetic`
+resultPixelLevelSemanticLabeling.json is written to save_dir and run_test's dict gains "pixel".  With --panoptic (and
+--gt_dir, cityscapes) the maps are scored as a panoptic segmentation on the device (evaluation/panoptic.py): the PQ
+table follows, resultPanopticSemanticLabeling.json is written and the dict gains "panoptic"; --save_panoptic writes
+the maps in COCO panoptic format under `<save_dir>/panoptic/`.  `--dataset synthetic`
 feeds hash-generated uint8 arrays (no files)."""
 import os
 import sys
@@ -90,6 +93,13 @@ def run_test(opt, evaluate=True):
         gt_files = instance_level.find_gt_files(opt.gt_dir, protocol)
         evaluator = instance_level.InstanceLevelEvaluator(protocol)
     pixel = None
+    save_pan, pan_entries, pan_dir = getattr(opt, "save_panoptic", False), [], os.path.join(opt.save_dir, "panoptic")
+    pan = None
+    if getattr(opt, "panoptic", False):
+        from centerpoly_amd.datasets.evaluation import panoptic
+        if evaluator is None or opt.dataset not in panoptic.DATASETS:
+            raise ValueError("--panoptic needs --gt_dir and the cityscapes data set")
+        pan = panoptic.PanopticEvaluator(panoptic.CITYSCAPES)
     if getattr(opt, "pixel_iou", False):
         from centerpoly_amd.datasets.evaluation import pixel_level
         if evaluator is None:
@@ -107,13 +117,19 @@ def run_test(opt, evaluate=True):
             if evaluator is not None:
                 dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"], item["gt_table"],
                                                evaluator)
-            if save_ids or save_masks or pixel is not None:
+            if save_ids or save_masks or pixel is not None or pan is not None or save_pan:
                 file_name = dataset.coco.loadImgs(ids=[item["img_id"]])[0]["file_name"]
                 maps = detector.instances(res, image=b)                    # once for the files and the score
                 if save_ids or save_masks:
                     save_instances(file_name, maps)
                 if pixel is not None:
                     pixel.add_maps(maps, item["gt_ids"], file_name)
+                if pan is not None:
+                    pan.add_maps(maps, item["gt_ids"], file_name)               # two calls, nothing comes back
+                if save_pan:
+                    from centerpoly_amd.datasets.evaluation import panoptic as pan_files
+                    from centerpoly_amd.detectors import instances
+                    pan_entries.append(pan_files.save_panoptic(maps, pan_dir, instances.image_stem(file_name)))
             stamps.append(time.time())
         print("[{}/{}] ".format(ind, len(images)) + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
     if not evaluate:
@@ -127,6 +143,13 @@ def run_test(opt, evaluate=True):
         out["pixel"] = pixel.summarize()
         print(pixel_level.format_results(out["pixel"], pixel.protocol))
         pixel_level.write_results(out["pixel"], opt.save_dir)
+    if save_pan:                                                       # before the score, which may refuse the run
+        from centerpoly_amd.datasets.evaluation import panoptic as pan_files
+        pan_files.write_panoptic_json(pan_dir, pan_entries)
+    if pan is not None and evaluate:
+        out["panoptic"] = pan.results()
+        pan.print_table(out["panoptic"])
+        pan.write_json(opt.save_dir, out["panoptic"])
     return out
 
 
