@@ -14,37 +14,16 @@
 //                         A lane reads its 16 ids once, maps them once and then streams 16 mask bytes per mask.
 //                         Two launches, whatever n and G.
 // Integer atomics only: the result does not depend on the order of the additions.
-#include "cp_common.h"
+// The piece, span and run scheme and the loaders are pixel_pieces.h's.
+#include "pixel_pieces.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPiece = 16;                              // pixels per lane and step
-constexpr int kTile = kThreads * kPiece;                // pixels per workgroup and step
-constexpr int kIds = 65536;
 constexpr int kVoidBit = 0x8000;                        // table entry: (column + 1) | kVoidBit
 constexpr int kLdsCounters = 8192;                      // 32 KiB of counters: four workgroups and more per CU
 constexpr int kBatch = 4;                              // masks a lane loads before it counts them
 constexpr int kCacheSlots = 1024;                       // histogram: LDS cache entries per workgroup
 constexpr int kMaxMasks = 128, kMaxInst = 1024, kMaxVoid = 64;
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// 16 ids of one piece; pixels at and beyond `HW` read as the id before them (so they never start a run) and
-// are masked out by the caller through `valid`.
-__device__ __forceinline__ void load_ids(const uint16_t* ids, long long p0, int valid, bool fast, int (&v)[kPiece]) {
-  if (fast && valid == kPiece) {
-    const uint4 a = *reinterpret_cast<const uint4*>(ids + p0), b = *reinterpret_cast<const uint4*>(ids + p0 + 8);
-    const unsigned w[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { v[2 * k] = w[k] & 0xffff; v[2 * k + 1] = w[k] >> 16; }
-  } else {
-#pragma unroll
-    for (int k = 0; k < kPiece; ++k) v[k] = k < valid ? ids[p0 + k] : (k ? v[k - 1] : 0);
-  }
-}
 
 // ------------------------------------------------------------------ histogram --
 __device__ __forceinline__ void hist_add(int* keys, int* vals, int* hist, int id, int cnt) {
@@ -120,21 +99,6 @@ struct OverlapArgs {
   int n, G, slice;            // masks per workgroup
 };
 
-// bit 8j + 7 of the result is set where byte j of w is non-zero
-__device__ __forceinline__ unsigned nonzero_bytes(unsigned w) {
-  return (((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u;
-}
-
-// 16 mask bytes of one piece as four words; bytes at and beyond `valid` read as zero
-__device__ __forceinline__ u32x4 load_mask(const uint8_t* mp, int valid) {
-  if (valid == kPiece && aligned16(mp)) return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(mp));
-  unsigned w[4] = {0, 0, 0, 0};                                           // unaligned mask start or the span's tail
-#pragma unroll
-  for (int k = 0; k < kPiece; ++k)
-    if (k < valid) w[k >> 2] |= (unsigned)mp[k] << (8 * (k & 3));
-  return u32x4{w[0], w[1], w[2], w[3]};
-}
-
 // one piece of one mask into the mask's counter row c[G + 2]
 __device__ __forceinline__ void count_piece(u32x4 w, int* c, int G, const int (&code)[kPiece], unsigned edges,
                                             bool wave_same) {
@@ -186,7 +150,8 @@ __global__ __launch_bounds__(kThreads) void instance_overlaps_kernel(OverlapArgs
     const long long p0 = t0 + (long long)threadIdx.x * kPiece;
     // (a lane past the span's end keeps valid == 0 and walks along: the wave votes below need every lane)
     const int valid = (int)max(0LL, min((long long)kPiece, end - p0));
-    // the piece's ids -> table codes, once for all masks of the slice; `edges` bit k: pixel k starts a run
+    // the piece's ids -> table codes, once for all masks of the slice; `edges` bit k: pixel k starts a run (the
+    // padding repeats the id before it: no edge past `valid`)
     int code[kPiece];
     load_ids(a.ids, p0, valid, fast_ids, code);
     unsigned edges = 0;
@@ -206,7 +171,10 @@ __global__ __launch_bounds__(kThreads) void instance_overlaps_kernel(OverlapArgs
     for (int m = 0; m < ms; m += kBatch, mp += kBatch * a.HW) {           // kBatch loads in flight per lane
       u32x4 w[kBatch];
 #pragma unroll
-      for (int j = 0; j < kBatch; ++j) w[j] = m + j < ms ? load_mask(mp + j * a.HW, valid) : u32x4{0, 0, 0, 0};
+      for (int j = 0; j < kBatch; ++j) {                                  // (a mask starts wherever n * HW falls)
+        const uint8_t* mj = mp + j * a.HW;
+        w[j] = m + j < ms ? load_bytes<true>(mj, valid, aligned16(mj)) : u32x4{0, 0, 0, 0};
+      }
 #pragma unroll
       for (int j = 0; j < kBatch; ++j)
         if (m + j < ms) count_piece(w[j], cnt + (m + j) * cols, a.G, code, edges, wave_same);
@@ -222,13 +190,6 @@ __global__ __launch_bounds__(kThreads) void instance_overlaps_kernel(OverlapArgs
   }
 }
 
-// pixels per workgroup: whole tiles, about `want` workgroups over the image
-long long span_for(long long HW, long long want) {
-  const long long tiles = (HW + kTile - 1) / kTile;
-  const long long per = (tiles + want - 1) / want;
-  return per * kTile;
-}
-
 }  // namespace
 
 extern "C" int cp_id_histogram(const uint16_t* ids, int32_t H, int32_t W, int32_t* hist, void* stream) {
@@ -240,8 +201,7 @@ extern "C" int cp_id_histogram(const uint16_t* ids, int32_t H, int32_t W, int32_
   // one workgroup per CU: every workgroup ends with an atomic on the few ids that fill the image (road, sky), and
   // those serialise on one address
   const long long span = span_for(HW, 256);
-  hipLaunchKernelGGL(id_histogram_kernel, dim3((unsigned)((HW + span - 1) / span)), dim3(kThreads), 0, st, ids, HW, span,
-                     hist);
+  hipLaunchKernelGGL(id_histogram_kernel, dim3(span_blocks(HW, span)), dim3(kThreads), 0, st, ids, HW, span, hist);
   return cp_launch_status();
 }
 
@@ -271,7 +231,7 @@ extern "C" int cp_instance_overlaps(const uint8_t* masks, int32_t n, const uint1
   a.slice = min(n, kLdsCounters / (G + 2));
   const int slices = (n + a.slice - 1) / a.slice;
   a.span = span_for(HW, (1024 + slices - 1) / slices);
-  hipLaunchKernelGGL(instance_overlaps_kernel, dim3((unsigned)((HW + a.span - 1) / a.span), slices), dim3(kThreads),
+  hipLaunchKernelGGL(instance_overlaps_kernel, dim3(span_blocks(HW, a.span), slices), dim3(kThreads),
                      (size_t)a.slice * (G + 2) * sizeof(int), st, a);
   return cp_launch_status();
 }

@@ -17,13 +17,11 @@
 // Two launches, whatever n is.  Integer atomics only: the result does not depend on the order of the additions.
 #include <limits.h>
 
-#include "cp_common.h"
+#include "pixel_pieces.h"                               // the piece and its byte loader
 
 namespace {
 
 constexpr int kMaxInst = 128;
-constexpr int kThreads = 256;
-constexpr int kPiece = 16;                              // pixels per lane
 constexpr int kTW = 256, kTH = 16;                      // the tile: 16 pieces across, one row per 16 lanes
 constexpr int kBatch = 8;                               // planes a lane loads before it resolves them
 constexpr int kNone = 255;                              // no winner (rank byte and index value)
@@ -33,10 +31,7 @@ static_assert(kTW / kPiece * kTH == kThreads, "one piece per lane");
 constexpr int kWsIdx = 4, kWsVal = kWsIdx + kMaxInst, kWsLab = kWsVal + kMaxInst, kWsBox = kWsLab + kMaxInst;
 constexpr int kWsWords = kWsBox + 4 * kMaxInst;
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // before(i, j) of the header for two priorities (has_prio == false: the index alone)
 __device__ __forceinline__ bool before(bool has_prio, float pi, int i, float pj, int j) {
@@ -100,27 +95,13 @@ __global__ __launch_bounds__(kMaxInst * kParts) void instance_map_prepare_kernel
   if (t == 0) ws[0] = ranked;
 }
 
-// bit 8j + 7 of the result is set where byte j of w is non-zero
-__device__ __forceinline__ unsigned nonzero_bytes(unsigned w) {
-  return (((w & 0x7f7f7f7fu) + 0x7f7f7f7fu) | w) & 0x80808080u;
-}
-
 // bits 7, 15, 23, 31 of nz as bits 0..3 (the products of the four source bits fall on distinct positions: no carry)
 __device__ __forceinline__ unsigned pack4(unsigned nz) { return (((nz >> 7) & 0x01010101u) * 0x01020408u) >> 24; }
 
 // bits 0..3 of m as the bytes 0x00 / 0xff of a word (again distinct positions)
 __device__ __forceinline__ unsigned spread4(unsigned m) { return (((m & 0xfu) * 0x00204081u) & 0x01010101u) * 0xffu; }
 
-// 16 mask bytes of one piece as the 16-bit word of its non-zero pixels; bytes at and beyond `valid` read as zero
-__device__ __forceinline__ u32x4 load_piece(const uint8_t* mp, int valid) {
-  if (valid == kPiece && aligned16(mp)) return __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(mp));
-  unsigned w[4] = {0, 0, 0, 0};                          // an unaligned row or the row's tail
-#pragma unroll
-  for (int k = 0; k < kPiece; ++k)
-    if (k < valid) w[k >> 2] |= (unsigned)mp[k] << (8 * (k & 3));
-  return u32x4{w[0], w[1], w[2], w[3]};
-}
-
+// the 16 mask bytes of one piece as the 16-bit word of its non-zero pixels
 __device__ __forceinline__ unsigned cover_bits(u32x4 w) {
   return pack4(nonzero_bytes(w.x)) | pack4(nonzero_bytes(w.y)) << 4 | pack4(nonzero_bytes(w.z)) << 8 |
          pack4(nonzero_bytes(w.w)) << 12;
@@ -198,7 +179,10 @@ __global__ __launch_bounds__(kThreads) void instance_map_tile_kernel(MapArgs a) 
       if (e0 + j < listed && open) {
         const int r = s_list[e0 + j];
         if (y >= s_box[4 * r + 1] && y <= s_box[4 * r + 3]) span[j] = span_bits(x, s_box[4 * r], s_box[4 * r + 2]) & open;
-        if (span[j]) w[j] = load_piece(a.masks + (long long)s_idx[r] * a.HW + p, valid);
+        if (span[j]) {                                     // (an unaligned row or the row's tail: element loads)
+          const uint8_t* mp = a.masks + (long long)s_idx[r] * a.HW + p;
+          w[j] = load_bytes<true>(mp, valid, aligned16(mp));
+        }
       }
     }
 #pragma unroll

@@ -24,14 +24,11 @@
 //   matched IoUs in ascending row order onto the running float64 sum -- the order of the evaluator's loop.
 // Integer atomics only in the counting: the counts do not depend on the order of the additions.  The float64 sum is
 // divisions and additions, nothing a contraction could fuse.
-#include "cp_common.h"
+// The piece, span and run scheme, the loaders and the run walker are pixel_pieces.h's.
+#include "pixel_pieces.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPiece = 16;                              // pixels per lane and step
-constexpr int kTile = kThreads * kPiece;                // pixels per workgroup and step
-constexpr int kIds = 65536;
 constexpr int kMaxLabels = 64, kMaxRows = 1024, kMaxSlots = 255;
 constexpr int kWorkgroups = 256;                        // one per CU
 constexpr int kLdsCells = 15360;                        // dense regime: 60 KB of counters per workgroup
@@ -47,21 +44,6 @@ struct MatchTables {
   uint8_t flags[kMaxLabels];
 };
 
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// 16 ids from p0 on (`valid` of them inside the span), two 16-byte loads where the image is aligned
-__device__ __forceinline__ void load_ids(const uint16_t* __restrict__ ids, long long p0, int valid, bool fast, int* v) {
-  if (fast && valid == kPiece) {
-    const uint4 i0 = *reinterpret_cast<const uint4*>(ids + p0), i1 = *reinterpret_cast<const uint4*>(ids + p0 + 8);
-    const unsigned w[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
-#pragma unroll
-    for (int k = 0; k < 8; ++k) { v[2 * k] = w[k] & 0xffff; v[2 * k + 1] = w[k] >> 16; }
-  } else {
-#pragma unroll
-    for (int k = 0; k < kPiece; ++k) v[k] = k < valid ? ids[p0 + k] : 0;
-  }
-}
-
 __global__ __launch_bounds__(kThreads) void pan_clear_kernel(unsigned* __restrict__ presence_words,
                                                              int* __restrict__ pairs, int cells) {
   const int stride = gridDim.x * kThreads, first = blockIdx.x * kThreads + threadIdx.x;
@@ -71,9 +53,11 @@ __global__ __launch_bounds__(kThreads) void pan_clear_kernel(unsigned* __restric
 
 __global__ __launch_bounds__(kThreads) void pan_presence_kernel(const uint16_t* __restrict__ ids, long long HW,
                                                                 long long span, uint8_t* __restrict__ presence) {
-  const long long begin = (long long)blockIdx.x * span, end = min(begin + span, HW);
   const bool fast = aligned16(ids);
   int last = -1;
+  // (for_pieces' loop, written out: through the lambda the compiler no longer splits the whole pieces, which need no
+  // k < valid, from the tail)
+  const long long begin = (long long)blockIdx.x * span, end = min(begin + span, HW);
   for (long long t0 = begin; t0 < end; t0 += kTile) {
     const long long p0 = t0 + (long long)threadIdx.x * kPiece;
     const int valid = (int)min((long long)kPiece, end - p0);
@@ -163,47 +147,25 @@ __global__ __launch_bounds__(kThreads) void pan_count_kernel(CountArgs a) {
     for (int k = threadIdx.x; k < used; k += kThreads) cells[k] = 0;
     __syncthreads();
   }
-  const long long begin = (long long)blockIdx.x * a.span, end = min(begin + a.span, a.HW);
   const bool fast_index = aligned16(a.index), fast_ids = aligned16(a.ids);
-  int run_v = -1, run_c = -1;                                             // the lane's run: id, column,
-  unsigned run_row = 0, run_cnt = 0;                                      // the id's row, pixels so far
-  for (long long t0 = begin; t0 < end; t0 += kTile) {
-    const long long p0 = t0 + (long long)threadIdx.x * kPiece;
-    const int valid = (int)min((long long)kPiece, end - p0);
-    if (valid <= 0) break;                                                // (no wave-wide operation in the loop)
+  PairRun run;                                                            // the lane's run: id, column
+  unsigned run_row = 0;                                                   // the id's row
+  auto look = [&](bool id_changed, bool) { if (id_changed) run_row = a.rowtab[run.a]; };
+  auto flush = [&](unsigned cnt) {
+    if (run_row == kDropped) return;
+    const int cell = (int)run_row * C + run.b;
+    if (dense) atomicAdd(&cells[cell], cnt);
+    else atomicAdd(&a.pairs[cell], (int)cnt);
+  };
+  for_pieces(a.HW, a.span, [&](long long p0, int valid) {
     int v[kPiece], c[kPiece];
     load_ids(a.ids, p0, valid, fast_ids, v);
-    if (fast_index && valid == kPiece) {
-      const uint4 b = *reinterpret_cast<const uint4*>(a.index + p0);
-      const unsigned w[4] = {b.x, b.y, b.z, b.w};
+    load_bytes<false>(a.index + p0, valid, fast_index, c);
 #pragma unroll
-      for (int k = 0; k < kPiece; ++k) c[k] = min((int)(w[k >> 2] >> (8 * (k & 3)) & 0xff), a.n);
-    } else {
-#pragma unroll
-      for (int k = 0; k < kPiece; ++k) c[k] = k < valid ? min((int)a.index[p0 + k], a.n) : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < kPiece; ++k) {
-      if (k < valid) {
-        if (v[k] != run_v || c[k] != run_c) {
-          if (run_cnt && run_row != kDropped) {
-            const int cell = (int)run_row * C + run_c;
-            if (dense) atomicAdd(&cells[cell], run_cnt);
-            else atomicAdd(&a.pairs[cell], (int)run_cnt);
-          }
-          if (v[k] != run_v) { run_v = v[k]; run_row = a.rowtab[run_v]; }
-          run_c = c[k];
-          run_cnt = 0;
-        }
-        ++run_cnt;
-      }
-    }
-  }
-  if (run_cnt && run_row != kDropped) {
-    const int cell = (int)run_row * C + run_c;
-    if (dense) atomicAdd(&cells[cell], run_cnt);
-    else atomicAdd(&a.pairs[cell], (int)run_cnt);
-  }
+    for (int k = 0; k < kPiece; ++k) c[k] = min(c[k], a.n);
+    walk_pairs(run, v, c, valid, look, flush);
+  });
+  if (run.cnt) flush(run.cnt);
   if (dense) {
     __syncthreads();
     for (int k = threadIdx.x; k < used; k += kThreads) {
@@ -357,9 +319,8 @@ extern "C" int cp_panoptic_pairs(const uint8_t* index, int32_t n, const uint16_t
   const int cells = (kMaxRows + 1) * (n + 1);
   hipLaunchKernelGGL(pan_clear_kernel, dim3(min((cells + kThreads - 1) / kThreads, 4 * kWorkgroups)), dim3(kThreads), 0,
                      st, (unsigned*)presence, pairs, cells);
-  const long long tiles = (HW + kTile - 1) / kTile;
-  const long long span = (tiles + kWorkgroups - 1) / kWorkgroups * kTile;
-  const unsigned blocks = (unsigned)((HW + span - 1) / span);
+  const long long span = span_for(HW, kWorkgroups);
+  const unsigned blocks = span_blocks(HW, span);
   hipLaunchKernelGGL(pan_presence_kernel, dim3(blocks), dim3(kThreads), 0, st, gt_ids, HW, span, presence);
   hipLaunchKernelGGL(pan_compact_kernel, dim3(1), dim3(kOneThreads), 0, st, fl, presence, id_divisor, id_direct_below, L,
                      rowtab, seg);

@@ -15,14 +15,11 @@
 //                           one before.  At the end the workgroup sends its non-zero counters to global memory, one
 //                           atomic per bin and workgroup.
 // Two launches, whatever G.  Integer atomics only: the result does not depend on the order of the additions.
-#include "cp_common.h"
+// The piece, span and run scheme, the loaders and the run walker are pixel_pieces.h's.
+#include "pixel_pieces.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPiece = 16;                              // pixels per lane and step
-constexpr int kTile = kThreads * kPiece;                // pixels per workgroup and step
-constexpr int kIds = 65536;
 constexpr int kPrepBlocks = 64, kPrepThreads = 1024;    // kPrepBlocks * kPrepThreads == kIds
 constexpr int kMaxLabels = 64, kMaxInst = 1024;
 constexpr unsigned kNone = 0xff;                        // label / group code: outside the table / no group
@@ -34,8 +31,6 @@ struct HostTables {
   uint8_t pred_label[256];
   int8_t label_group[kMaxLabels];
 };
-
-__device__ __forceinline__ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 __global__ __launch_bounds__(kPrepThreads) void pixel_prepare_kernel(HostTables t, const int* __restrict__ inst_ids,
                                                                      int G, int id_divisor, int id_direct_below, int L,
@@ -104,47 +99,21 @@ __global__ __launch_bounds__(kThreads) void pixel_confusion_kernel(PixelArgs a) 
   __syncthreads();
   unsigned* s_conf = counters;
   unsigned* s_inst = counters + nconf;
-  const long long begin = (long long)blockIdx.x * a.span, end = min(begin + a.span, a.HW);
   const bool fast_pred = aligned16(a.pred), fast_ids = aligned16(a.ids);
-  int run_v = -1, run_q = -1;                                             // the lane's run: id, prediction byte,
-  unsigned run_e = 0, run_pe = 0, run_cnt = 0, bad0 = 0, bad1 = 0;        // their entries, pixels so far
-  for (long long t0 = begin; t0 < end; t0 += kTile) {
-    const long long p0 = t0 + (long long)threadIdx.x * kPiece;
-    const int valid = (int)min((long long)kPiece, end - p0);
-    if (valid <= 0) break;                                                // (no wave-wide operation below)
+  PairRun run;                                                            // the lane's run: id, prediction byte
+  unsigned run_e = 0, run_pe = 0, bad0 = 0, bad1 = 0;                     // their entries
+  auto look = [&](bool id_changed, bool pred_changed) {
+    if (id_changed) run_e = a.table[run.a];
+    if (pred_changed) run_pe = s_ptab[run.b];
+  };
+  auto flush = [&](unsigned cnt) { count_run(run_e, run_pe, cnt, a.L, s_conf, s_inst, bad0, bad1); };
+  for_pieces(a.HW, a.span, [&](long long p0, int valid) {
     int v[kPiece], q[kPiece];
-    if (fast_ids && valid == kPiece) {
-      const uint4 i0 = *reinterpret_cast<const uint4*>(a.ids + p0), i1 = *reinterpret_cast<const uint4*>(a.ids + p0 + 8);
-      const unsigned w[8] = {i0.x, i0.y, i0.z, i0.w, i1.x, i1.y, i1.z, i1.w};
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { v[2 * k] = w[k] & 0xffff; v[2 * k + 1] = w[k] >> 16; }
-    } else {
-#pragma unroll
-      for (int k = 0; k < kPiece; ++k) v[k] = k < valid ? a.ids[p0 + k] : 0;
-    }
-    if (fast_pred && valid == kPiece) {
-      const uint4 b = *reinterpret_cast<const uint4*>(a.pred + p0);
-      const unsigned w[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-      for (int k = 0; k < kPiece; ++k) q[k] = w[k >> 2] >> (8 * (k & 3)) & 0xff;
-    } else {
-#pragma unroll
-      for (int k = 0; k < kPiece; ++k) q[k] = k < valid ? a.pred[p0 + k] : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < kPiece; ++k) {
-      if (k < valid) {
-        if (v[k] != run_v || q[k] != run_q) {
-          if (run_cnt) count_run(run_e, run_pe, run_cnt, a.L, s_conf, s_inst, bad0, bad1);
-          if (v[k] != run_v) { run_v = v[k]; run_e = a.table[run_v]; }
-          if (q[k] != run_q) { run_q = q[k]; run_pe = s_ptab[run_q]; }
-          run_cnt = 0;
-        }
-        ++run_cnt;
-      }
-    }
-  }
-  if (run_cnt) count_run(run_e, run_pe, run_cnt, a.L, s_conf, s_inst, bad0, bad1);
+    load_ids(a.ids, p0, valid, fast_ids, v);
+    load_bytes<false>(a.pred + p0, valid, fast_pred, q);
+    walk_pairs(run, v, q, valid, look, flush);
+  });
+  if (run.cnt) flush(run.cnt);
   if (bad0) atomicAdd(&s_bad[0], bad0);
   if (bad1) atomicAdd(&s_bad[1], bad1);
   __syncthreads();
@@ -186,9 +155,8 @@ extern "C" int cp_pixel_confusion(const uint8_t* pred, const uint8_t* pred_label
   PixelArgs a;
   a.pred = pred; a.ids = gt_ids; a.table = table; a.ptab = ptab; a.conf = (unsigned long long*)conf; a.inst = inst;
   a.bad = bad; a.HW = HW; a.L = L; a.G = G;
-  const long long tiles = (HW + kTile - 1) / kTile;
-  a.span = (tiles + kWorkgroups - 1) / kWorkgroups * kTile;
-  hipLaunchKernelGGL(pixel_confusion_kernel, dim3((unsigned)((HW + a.span - 1) / a.span)), dim3(kThreads),
+  a.span = span_for(HW, kWorkgroups);
+  hipLaunchKernelGGL(pixel_confusion_kernel, dim3(span_blocks(HW, a.span)), dim3(kThreads),
                      (size_t)(L * L + 3 * G) * sizeof(unsigned), st, a);
   return cp_launch_status();
 }

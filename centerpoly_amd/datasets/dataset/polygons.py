@@ -207,13 +207,7 @@ class CityscapesWriterMixin(object):
             rows_dev = torch.full((1, 2 * N + 7), float("-inf"), dtype=torch.float32, device=dev)
             R = 1
         S = min(R, il.MAX_MASKS)                                          # slots drawn and counted
-        if torch.is_tensor(gt_ids):
-            gt_dev = gt_ids
-        else:
-            gt_ids = np.ascontiguousarray(gt_ids)
-            if gt_ids.dtype != np.uint16:
-                raise ValueError("gt_ids must be uint16 (see read_gt_ids), got %s" % gt_ids.dtype)
-            gt_dev = torch.from_numpy(gt_ids.view(np.int16)).to(dev)
+        gt_dev = il.device_ids(gt_ids, dev)
         if tuple(gt_dev.shape) != (H, W):
             raise ValueError("the id image is %s, the result canvas is %s" % (tuple(gt_dev.shape), (H, W)))
         if gt_table is None:
@@ -414,13 +408,7 @@ class ClassWriterMixin(object):
             rows_dev = torch.full((1, 2 * N + 7), float("-inf"), dtype=torch.float32, device=dev)
             R = 1
         S = min(R, il.MAX_MASKS)                                          # slots drawn and counted
-        if torch.is_tensor(gt_ids):
-            gt_dev = gt_ids
-        else:
-            gt_ids = np.ascontiguousarray(gt_ids)
-            if gt_ids.dtype != np.uint16:
-                raise ValueError("gt_ids must be uint16 (see read_gt_ids), got %s" % gt_ids.dtype)
-            gt_dev = torch.from_numpy(gt_ids.view(np.int16)).to(dev)
+        gt_dev = il.device_ids(gt_ids, dev)
         H, W = (int(v) for v in gt_dev.shape)
         if gt_table is None:
             gt_table = il.gt_instances(il.device_histogram(gt_dev), proto)

@@ -121,6 +121,23 @@ def read_gt_ids(path):
     return np.ascontiguousarray(arr.astype(np.uint16))
 
 
+def device_ids(gt_ids, device, what=""):
+    """The id image as the kernels take it, a device tensor of 16-bit integers: a host uint16 array is uploaded to
+    `device` with its bits kept (as int16), a tensor is passed on where it is and only its dtype is checked.  `what`
+    names the image in the error.  The shape is the caller's to check."""
+    import torch
+    what = what and what + ": "
+    if torch.is_tensor(gt_ids):
+        if gt_ids.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            raise ValueError("%sthe ground truth is %s: gt_ids must be uint16 (see read_gt_ids) or a device tensor of "
+                             "16-bit integers" % (what, gt_ids.dtype))
+        return gt_ids
+    gt_ids = np.ascontiguousarray(gt_ids)
+    if gt_ids.dtype != np.uint16:
+        raise ValueError("%sgt_ids must be uint16 (see read_gt_ids), got %s" % (what, gt_ids.dtype))
+    return torch.from_numpy(gt_ids.view(np.int16)).to(device)
+
+
 def find_gt_files(gt_dir, protocol=CITYSCAPES):
     """{image key: path} of every ground-truth file below gt_dir (Cityscapes: *_gtFine_instanceIds.png by image
     prefix; KITTI: *.png by base name; IDD: <city>/<frame>_gtFine_instanceids.png by `<city>/<frame>`)."""
@@ -195,12 +212,8 @@ class InstanceLevelEvaluator(object):
         image: a host uint16 [H, W] array, or a device tensor of 16-bit elements holding those bits."""
         import torch
         n = int(masks_dev.shape[0])
-        if not torch.is_tensor(gt_ids):
-            gt_ids = np.ascontiguousarray(gt_ids)
-            if gt_ids.dtype != np.uint16:
-                raise ValueError("gt_ids must be uint16 (see read_gt_ids), got %s" % gt_ids.dtype)
-            dev = masks_dev.device if n else torch.device("cuda")         # (an image without predictions still
-            gt_ids = torch.from_numpy(gt_ids.view(np.int16)).to(dev)      # has ground truth to count; bits are kept)
+        # (an image without predictions still has ground truth to count: on the default device)
+        gt_ids = device_ids(gt_ids, masks_dev.device if n else torch.device("cuda"))
         if len(label_ids) != n or len(confidences) != n:
             raise ValueError("%d masks, %d labels, %d confidences" % (n, len(label_ids), len(confidences)))
         if tuple(masks_dev.shape[1:]) != tuple(gt_ids.shape):

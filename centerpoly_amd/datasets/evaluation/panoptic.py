@@ -108,15 +108,10 @@ class PanopticEvaluator(object):
         labels = np.ascontiguousarray(pred_label, np.int32).reshape(-1)
         if len(labels) < n:
             raise ValueError("%s: %d slot labels for %d slots" % (what, len(labels), n))
-        if not torch.is_tensor(gt_ids_dev):
-            gt = np.ascontiguousarray(gt_ids_dev)
-            if gt.dtype != np.uint16:
-                raise ValueError("%s: gt_ids must be uint16 (see read_gt_ids), got %s" % (what, gt.dtype))
-            gt_ids_dev = torch.from_numpy(gt.view(np.int16)).to(index_dev.device)
-        if gt_ids_dev.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) \
-                or tuple(gt_ids_dev.shape) != tuple(index_dev.shape):
-            raise ValueError("%s: the ground truth is %s %s, the prediction is %s"
-                             % (what, gt_ids_dev.dtype, tuple(gt_ids_dev.shape), tuple(index_dev.shape)))
+        gt_ids_dev = il.device_ids(gt_ids_dev, index_dev.device, what)
+        if tuple(gt_ids_dev.shape) != tuple(index_dev.shape):
+            raise ValueError("%s: the ground truth is %s, the prediction is %s"
+                             % (what, tuple(gt_ids_dev.shape), tuple(index_dev.shape)))
         H, W = (int(v) for v in index_dev.shape)
         t = self._tables(index_dev.device)
         lib, st = _C.lib(), _C.stream()

@@ -186,11 +186,7 @@ class PixelLevelEvaluator(object):
         if pred_dev.dim() != 2 or pred_dev.dtype != torch.uint8:
             raise ValueError("%s: the prediction must be uint8 [H, W], got %s %s"
                              % (what, pred_dev.dtype, tuple(pred_dev.shape)))
-        if not torch.is_tensor(gt_ids):
-            gt_ids = np.ascontiguousarray(gt_ids)
-            if gt_ids.dtype != np.uint16:
-                raise ValueError("%s: gt_ids must be uint16 (see read_gt_ids), got %s" % (what, gt_ids.dtype))
-            gt_ids = torch.from_numpy(gt_ids.view(np.int16)).to(pred_dev.device)
+        gt_ids = il.device_ids(gt_ids, pred_dev.device, what)
         if tuple(gt_ids.shape) != tuple(pred_dev.shape):
             raise ValueError("%s: the ground truth is %s, the prediction is %s"
                              % (what, tuple(gt_ids.shape), tuple(pred_dev.shape)))
