@@ -136,7 +136,7 @@ __global__ __launch_bounds__(THREADS) void bn_apply_kernel(const float* __restri
       for (int k = 0; k < 4; ++k) {
         v[k] = v[k] * sc + sh;
         if (res) v[k] += rv[j][k];
-        if (relu) v[k] = fmaxf(v[k], 0.f);
+        if (relu) v[k] = cp_relu(v[k]);
       }
       *reinterpret_cast<f32x4*>(y + base + i) = v;
     }
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(THREADS) void bn_apply_kernel(const float* __restri
     for (long long i = i0 + threadIdx.x; i < i1; i += THREADS) {
       float v = x[base + i] * sc + sh;
       if (res) v += res[base + i];
-      y[base + i] = relu ? fmaxf(v, 0.f) : v;
+      y[base + i] = relu ? cp_relu(v) : v;
     }
   }
 }

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256, 2) void conv_base_pair_kernel(PairArgs a) {
       const bool inside = iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
       float o[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) o[q] = inside ? fmaxf(acc[q] + b0r[q], 0.f) : 0.f;
+      for (int q = 0; q < 4; ++q) o[q] = inside ? cp_relu(acc[q] + b0r[q]) : 0.f;
       unsigned hi[2], lo[2];
       psplit2(o[0], o[1], hi[0], lo[0]);
       psplit2(o[2], o[3], hi[1], lo[1]);
@@ -250,7 +250,7 @@ __global__ __launch_bounds__(256, 2) void conv_base_pair_kernel(PairArgs a) {
         for (int m = 0; m < 2; ++m)
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            ob[((long long)(16 * m + 4 * g + q) * a.Ho + oy) * a.Wo + ox] = fmaxf(acc[m][q] + b1r[m][q], 0.f);
+            ob[((long long)(16 * m + 4 * g + q) * a.Ho + oy) * a.Wo + ox] = cp_relu(acc[m][q] + b1r[m][q]);
       }
     }
   }

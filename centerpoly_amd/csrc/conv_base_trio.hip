@@ -289,7 +289,7 @@ __global__ __launch_bounds__(NT, 1) void conv_base_trio_kernel(TrioArgs a) {
       const bool inside = sy >= 0 && sy < a.H && sx >= 0 && sx < a.W;
       float o[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) o[q] = inside ? fmaxf(acc[n][q] + bsr[q], 0.f) : 0.f;
+      for (int q = 0; q < 4; ++q) o[q] = inside ? cp_relu(acc[n][q] + bsr[q]) : 0.f;
       unsigned hi[2], lo[2];
       tsplit2(o[0], o[1], hi[0], lo[0]);
       tsplit2(o[2], o[3], hi[1], lo[1]);
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(NT, 1) void conv_base_trio_kernel(TrioArgs a) {
       const bool inside = iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
       float o[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) o[q] = inside ? fmaxf(acc[n][q] + b0r[q], 0.f) : 0.f;
+      for (int q = 0; q < 4; ++q) o[q] = inside ? cp_relu(acc[n][q] + b0r[q]) : 0.f;
       unsigned hi[2], lo[2];
       tsplit2(o[0], o[1], hi[0], lo[0]);
       tsplit2(o[2], o[3], hi[1], lo[1]);
@@ -378,7 +378,7 @@ __global__ __launch_bounds__(NT, 1) void conv_base_trio_kernel(TrioArgs a) {
       float* ob = a.out + (long long)s.b * C1 * a.Ho * a.Wo;
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        ob[((long long)(16 * cm + 4 * g + q) * a.Ho + oy) * a.Wo + ox] = fmaxf(acc[q] + b1r[q], 0.f);
+        ob[((long long)(16 * cm + 4 * g + q) * a.Ho + oy) * a.Wo + ox] = cp_relu(acc[q] + b1r[q]);
     }
   };
 

@@ -158,7 +158,7 @@ __global__ __launch_bounds__(256) void conv3x3_c16_kernel(ConvArgs a) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             float v = acc[m][tx][q] + bias_r[m][q];
-            if (a.relu) v = fmaxf(v, 0.f);
+            if (a.relu) v = cp_relu(v);
             ob[((long long)(16 * m + 4 * g + q) * a.Ho + oy) * a.Wo + ox] = v;
           }
       }
@@ -359,7 +359,7 @@ __global__ __launch_bounds__(256) void conv3x3_c16_bf16_kernel(ConvArgs a) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             float v = acc[m][tx][q] + bias_r[m][q];
-            if (a.relu) v = fmaxf(v, 0.f);
+            if (a.relu) v = cp_relu(v);
             ob[((long long)(16 * m + 4 * g + q) * a.Ho + oy) * a.Wo + ox] = v;
           }
       }
@@ -452,7 +452,7 @@ __global__ __launch_bounds__(256) void conv7x7_c3_kernel(ConvArgs a) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           float v = acc0[q] + acc1[q] + bias_r[q];
-          if (a.relu) v = fmaxf(v, 0.f);
+          if (a.relu) v = cp_relu(v);
           ob[((long long)(4 * g + q) * a.Ho + oy) * a.Wo + ox] = v;
         }
       }

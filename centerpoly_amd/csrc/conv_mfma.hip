@@ -464,7 +464,7 @@ __global__ __launch_bounds__(256 * KS, KS > 1 ? (ST > 1 && TAPS == 9 ? 1 : 4) : 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float v = acc[m][n][r] + bv[r];
-          if (a.relu) v = fmaxf(v, 0.f);
+          if (a.relu) v = cp_relu(v);
           const __bf16 hh = (__bf16)v;
           h[r] = hh;
           l[r] = (__bf16)(v - (float)hh);
@@ -527,7 +527,7 @@ __global__ __launch_bounds__(256 * KS, KS > 1 ? (ST > 1 && TAPS == 9 ? 1 : 4) : 
       for (int r = 0; r < 4; ++r) {
         float t = acc[m][n][r] + bv;
         if (a.res) t += rv[n][r];
-        if (a.relu) t = fmaxf(t, 0.f);
+        if (a.relu) t = cp_relu(t);
         if (a.mask && !(mv[n][r] > 0.f)) t = 0.f;
         v[r] = t;
         csum[n & 1] += (off[n] != EOOB && x + r < a.Wo) ? t : 0.f;

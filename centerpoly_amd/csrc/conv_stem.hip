@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256, 2) void conv_stem_kernel(StemArgs a) {
         const int y = y0 + wid * 2 + (n >> 1), x = x0 + (n & 1) * 16 + c;
         const bool ok = cot0 + col < a.Cout && y < a.Ho && x < a.Wo;
         float v = acc[m][n][r] + bv;
-        if (a.relu) v = fmaxf(v, 0.f);
+        if (a.relu) v = cp_relu(v);
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rs_o,
                                               ok ? ((unsigned)col * (unsigned)HWo + (unsigned)(y * a.Wo + x)) * 4u : OOB, 0, 0);
       }

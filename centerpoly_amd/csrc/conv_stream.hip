@@ -256,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_stream_kernel(StreamArgs a) {
         for (int r = 0; r < 4; ++r) {
           float x = s[r] + bv[m];
           if (a.res) x += rv[m][n][r];
-          if (a.relu) x = fmaxf(x, 0.f);
+          if (a.relu) x = cp_relu(x);
           o[r] = x;
         }
         if constexpr (VEC) {

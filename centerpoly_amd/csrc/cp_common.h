@@ -20,6 +20,21 @@ static inline size_t cp_align_up(size_t v, size_t a) { return (v + a - 1) / a * 
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// The library's one ReLU, as torch.relu computes it: v where v is a NaN, fmaxf(v, 0.f) otherwise.  fmaxf alone
+// (v_max_f32) returns the operand that is not a NaN, so it turned a NaN into 0.  IEEE 754-2019 maximum is one
+// instruction on gfx950 (v_maximum3_f32 v, 0, 0) and gives every other value, -0, denormals and the infinities included,
+// the bits of fmaxf(v, 0.f); `v != v ? v : fmaxf(v, 0.f)` is a compare and a select more and cost the inference step
+// 0.6 %.  Both claims rest on the compiler's lowering of the builtin: the guard is
+// test_relu_keeps_the_bits_of_every_other_value (tests/test_nonfinite.py), a sweep of float32 bit patterns on the device.
+__device__ __forceinline__ float cp_relu(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+
+__device__ __forceinline__ f32x4 cp_relu(f32x4 v) {
+  return f32x4{cp_relu(v[0]), cp_relu(v[1]), cp_relu(v[2]), cp_relu(v[3])};
+}
+
+// torch.clamp(v, lo, hi) for lo <= hi: a NaN stays a NaN, every other value takes fminf(fmaxf(v, lo), hi).
+__device__ __forceinline__ float cp_clamp(float v, float lo, float hi) { return v != v ? v : fminf(fmaxf(v, lo), hi); }
+
 // Wave-wide sum (64 lanes) through DPP/shuffles.
 __device__ __forceinline__ float cp_wave_sum(float v) {
 #pragma unroll

@@ -274,7 +274,7 @@ __global__ __launch_bounds__(256, WPS) void dcn_fwd_pipe_kernel(DcnFwdArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         v[r] = acc[i][j][r] * sc + sh;
-        if (a.relu && !raw) v[r] = fmaxf(v[r], 0.f);
+        if (a.relu && !raw) v[r] = cp_relu(v[r]);
       }
       float* dst = ob + (long long)co * HWo + pp;
       if (pp + 3 < HWo && (HWo & 3) == 0) {
@@ -485,7 +485,7 @@ __global__ __launch_bounds__(256, WPS) void dcn_fwd_pipe_bf16_kernel(DcnFwdArgs 
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         v[r] = acc[i][j][r] * sc + sh;
-        if (a.relu && !raw) v[r] = fmaxf(v[r], 0.f);
+        if (a.relu && !raw) v[r] = cp_relu(v[r]);
       }
       float* dst = ob + (long long)co * HWo + pp;
       if (pp + 3 < HWo && (HWo & 3) == 0) {

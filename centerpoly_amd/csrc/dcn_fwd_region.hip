@@ -361,8 +361,8 @@ __global__ __launch_bounds__(256, 2) void dcn_fwd_region_kernel(RegionArgs a) {
       const float pxf = (float)(x - 1 + kx) + ox[t];
       const bool inside = ok && py > -1.f && pxf > -1.f && py < (float)H && pxf < (float)W;
       const float fy = floorf(py), fx = floorf(pxf);
-      const float ly = inside ? py - fy : 0.f;   // (!inside: weights exactly +0, whatever the offsets hold)
-      if (!inside) m = 0.f;
+      const float ly = inside ? py - fy : 0.f;   // (!inside: weights exactly +0, whatever the offsets hold ...
+      if (!inside) m = (ok && m != m) ? m : 0.f;   // (a NaN mask stays: oracle/dcn.py's 0 * mask, as in the gather kernels)
       ru0[t] = (1.f - ly) * m;
       ru1[t] = ly * m;
       rlx[t] = inside ? pxf - fx : 0.f;
@@ -644,7 +644,7 @@ __global__ __launch_bounds__(256, 2) void dcn_fwd_region_kernel(RegionArgs a) {
           float o = acc[r][ct][i];
           if (a.ksplit <= 1) {                              // (a slice of a K split leaves its raw sums)
             o = o * sc + sh;
-            if (a.relu) o = fmaxf(o, 0.f);
+            if (a.relu) o = cp_relu(o);
           }
           ot[((col + 4 * kg) * 2 + r) * 32 + px] = o;
         }

@@ -44,7 +44,7 @@ __device__ inline void cp_dcn_slices_values(const float* (&p)[N], long long stri
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     v[k] = v[k] * sc + sh;
-    if (relu) v[k] = fmaxf(v[k], 0.f);
+    if (relu) v[k] = cp_relu(v[k]);
   }
 }
 

@@ -67,11 +67,13 @@ __global__ __launch_bounds__(256) void conv1x1_act_kernel(HeadArgs a) {
       const int c = min(c0 + u, c_end - 1);        //  runtime-indexed v[] / acc[] goes to scratch)
       const bool live = c0 + u < c_end;            // wave-uniform
       const float ib = a.in_bias ? a.in_bias[c] : 0.f;
-      f32x4 x = v[u];
+      // a slot past the wave's channels re-read its last channel: it enters as 0, not as that channel under a weight
+      // of 0 (0 * Inf would turn the channel's own Inf into a NaN)
+      f32x4 x = live ? v[u] : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         x[k] += ib;
-        if (a.relu_in) x[k] = fmaxf(x[k], 0.f);
+        if (a.relu_in) x[k] = cp_relu(x[k]);
       }
       const float* wr = a.wt + (long long)c * a.Cout;
       // <2 x float> arithmetic -> v_pk_fma_f32: two FMAs per instruction (the 32-output head is

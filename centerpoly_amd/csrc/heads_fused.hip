@@ -204,7 +204,7 @@ __global__ __launch_bounds__(256, 2) void conv_heads_fused_kernel(HeadsArgs a) {
         bf16x8 fh, fl;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const float v = fmaxf(acc[2 * p + (j >> 2)][n][j & 3] + bia[j], 0.f);
+          const float v = cp_relu(acc[2 * p + (j >> 2)][n][j & 3] + bia[j]);
           const __bf16 h = (__bf16)v;
           fh[j] = h;
           fl[j] = (__bf16)(v - (float)h);
@@ -382,7 +382,7 @@ __global__ __launch_bounds__(512, 2) void conv_heads_fused_res_kernel(HeadsArgs 
         bf16x8 fh, fl;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const float v = fmaxf(acc[2 * p + (j >> 2)][n][j & 3] + bia[j], 0.f);
+          const float v = cp_relu(acc[2 * p + (j >> 2)][n][j & 3] + bia[j]);
           const __bf16 h = (__bf16)v;
           fh[j] = h;
           fl[j] = (__bf16)(v - (float)h);

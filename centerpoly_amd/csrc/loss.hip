@@ -18,7 +18,7 @@ constexpr float CLAMP_HI = (float)(1 - 1e-4);
 __device__ __forceinline__ void focal_elem(float x, float g, float& p_out, float& pos, float& neg,
                                            float& npos) {
   float p = 1.f / (1.f + expf(-x));
-  p = fminf(fmaxf(p, CLAMP_LO), CLAMP_HI);
+  p = cp_clamp(p, CLAMP_LO, CLAMP_HI);
   p_out = p;
   if (g == 1.f) {
     const float q = 1.f - p;

@@ -337,13 +337,13 @@ __global__ __launch_bounds__(256) void bias_act_kernel(float* __restrict__ y,
       v[0] += r[0]; v[1] += r[1]; v[2] += r[2]; v[3] += r[3];
     }
     v[0] += bv; v[1] += bv; v[2] += bv; v[3] += bv;
-    if (relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+    if (relu) v = cp_relu(v);
     reinterpret_cast<f32x4*>(yp)[i] = v;
   }
   if (blockIdx.x == 0 && threadIdx.x < (HW & 3)) {
     const long long i = (n4 << 2) + threadIdx.x;
     float v = yp[i] + bv + (rp ? rp[i] : 0.f);
-    yp[i] = relu ? fmaxf(v, 0.f) : v;
+    yp[i] = relu ? cp_relu(v) : v;
   }
 }
 }  // namespace

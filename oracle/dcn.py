@@ -57,7 +57,9 @@ def _bilinear_columns(x, offset, mask, kh, kw, stride, pad, dil, dg):
                 ok = (yi >= 0) & (yi <= H - 1) & (xi >= 0) & (xi <= W - 1) & inside
                 idx = (yi.clamp(0, H - 1) * W + xi.clamp(0, W - 1)).view(B, 1, Ho * Wo)
                 v = torch.gather(xg, 2, idx.expand(B, cpg, Ho * Wo)).view(B, cpg, Ho, Wo)
-                return v * ok.to(dt)
+                # a neighbour outside the image is not read (as in dcn_im2col.py): where(), not a product with 0,
+                # so that a non-finite border pixel does not reach the samples whose index was clamped onto it
+                return torch.where(ok, v, torch.zeros((), dtype=dt, device=dev))
 
             val = (hy * hx) * corner(y0i, x0i) + (hy * lx) * corner(y0i, x1i) \
                 + (ly * hx) * corner(y1i, x0i) + (ly * lx) * corner(y1i, x1i)
