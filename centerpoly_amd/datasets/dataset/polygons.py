@@ -183,7 +183,7 @@ class CityscapesWriterMixin(object):
         names = cls.class_name[1:]
         return np.array([[cls.label_to_id[c], 0 if c in cls.no_mask_labels else 1] for c in names], np.int32)
 
-    def score_instances_device(self, rows_dev, gt_ids, gt_table=None, evaluator=None):
+    def score_instances_device(self, rows_dev, gt_ids, gt_table=None, evaluator=None, boundary=None):
         """One image scored from its detection rows without a pass through host Python: device float32 rows
         [R, 2N + 7] in the layout cp_polydet_post_process writes (x1,y1,x2,y2,score,cls,poly,depth; R <= 1024)
         -> cp_writer_instances -> cp_instance_masks -> cp_instance_overlaps on all slots, then ONE read of the small
@@ -191,7 +191,10 @@ class CityscapesWriterMixin(object):
         instance_level.gt_instances gives for it (a loader worker can make it from np.bincount), by default taken
         from cp_id_histogram.  The writer's selection (label has masks, more than 100 pixels) is applied to the rows
         of the tables; with an `evaluator` the kept rows are added to it (add_counts).  Returns the tables:
-        n, src, labels, conf (float32), conf_text, counts, kept, gt_table, inter, void."""
+        n, src, labels, conf (float32), conf_text, counts, kept, gt_table, inter, void.
+        boundary: an evaluation.boundary.BoundaryEvaluator, or None.  With one, the masks also go through
+        cp_boundary_overlaps (bounds: the polygons' boxes grown by the writer's radius-2 dilation); the band tables come
+        back in the same read, are returned as b_inter, b_pred, b_gt and band_width, and the kept rows are added to it."""
         import ctypes
 
         import torch
@@ -220,7 +223,13 @@ class CityscapesWriterMixin(object):
         # one upload: the ids of interest and the void ids; one buffer for everything that comes back
         ids = torch.from_numpy(np.concatenate([gt_table[:G0, 0], il.VOID_IDS]).astype(np.int32)).to(dev)
         fw = (R + 3) // 4
-        out = torch.empty((4 + 3 * R + 3 * S + fw + S * G0,), dtype=torch.int32, device=dev)
+        o_band = 4 + 3 * R + 3 * S + fw + S * G0                          # the band tables, after everything else
+        if boundary is not None:
+            from ...detectors import instances
+            from ..evaluation import boundary as bd
+            band_d = boundary.band_width(H, W)
+        out = torch.empty((o_band + (bd.table_words(S, G0) if boundary is not None else 0),), dtype=torch.int32,
+                          device=dev)
         o_src, o_lab, o_conf = 4, 4 + R, 4 + 2 * R
         o_cnt = 4 + 3 * R
         o_void, o_pix, o_flag, o_int = o_cnt + S, o_cnt + 2 * S, o_cnt + 3 * S, o_cnt + 3 * S + fw
@@ -238,6 +247,9 @@ class CityscapesWriterMixin(object):
         _C.check(L.cp_instance_overlaps(_C.ptr(masks), S, _C.ptr(gt_dev), H, W, _C.ptr(ids), G0,
                                         ctypes.c_void_p(ids.data_ptr() + 4 * G0), len(il.VOID_IDS), at(o_int),
                                         at(o_void), at(o_pix), _C.ptr(ws), nbytes, st), "cp_instance_overlaps")
+        if boundary is not None:
+            bounds = instances.vertex_bounds(poly[:S], instances.MARGIN["cityscapes"], (W, H))
+            bd.enqueue_tables(masks, bounds, gt_dev, band_d, ids, G0, out, o_band)
         host = out.cpu().numpy()
         n = int(host[0])
         if n > il.MAX_MASKS:
@@ -260,6 +272,12 @@ class CityscapesWriterMixin(object):
             pix = host[o_pix:o_pix + n].astype(np.int64)
             evaluator.add_counts(gt_table, res["labels"][kept].tolist(), [float(c) for c in res["conf_text"]],
                                  pix[kept], res["void"][kept], inter[kept])
+        if boundary is not None:
+            b_inter, b_pred, b_gt = bd.read_tables(host, o_band, S, G0, n, masks, bounds, gt_dev, band_d, gt_table)
+            res.update(b_inter=b_inter, b_pred=b_pred, b_gt=b_gt, band_width=band_d)
+            pix = host[o_pix:o_pix + n].astype(np.int64)
+            boundary.add_counts(gt_table, res["labels"][kept].tolist(), [float(c) for c in res["conf_text"]],
+                                pix[kept], res["void"][kept], inter[kept], b_pred[kept], b_gt, b_inter[kept])
         return res
 
     def format_and_write_to_cityscapes(self, all_bboxes, save_dir, evaluator=None, gt_files=None, write_files=True):
@@ -385,14 +403,17 @@ class ClassWriterMixin(object):
                  "cp_class_instance_masks")
         return masks, counts
 
-    def score_instances_device(self, rows_dev, gt_ids, gt_table=None, evaluator=None):
+    def score_instances_device(self, rows_dev, gt_ids, gt_table=None, evaluator=None, boundary=None):
         """One image scored from its detection rows without a pass through host Python, the KITTI / IDD way: device
         float32 rows [R, 2N + 7] (x1,y1,x2,y2,score,cls,poly,depth; R <= 1024) -> cp_class_writer_instances ->
         cp_class_instance_masks -> cp_instance_overlaps on all slots, then ONE read of the small tables.  The canvas
         is the id image's (an image of another size is refused where both files are known: eval_images, run_eval).
         gt_ids, gt_table as CityscapesWriterMixin.score_instances_device takes them.  With an `evaluator` the
         instances are added to it in the order of the text lines.  Returns the tables in that order: n, src, labels,
-        conf (float32), conf_text, counts, text_index, draw_slot, gt_table, inter, void."""
+        conf (float32), conf_text, counts, text_index, draw_slot, gt_table, inter, void.
+        boundary: an evaluation.boundary.BoundaryEvaluator, or None.  With one, the masks also go through
+        cp_boundary_overlaps (bounds: the polygons' boxes, which PIL's fill stays inside); the band tables come back in
+        the same read, are returned as b_inter, b_pred, b_gt (text-line order) and band_width, and are added to it."""
         import ctypes
 
         import torch
@@ -424,7 +445,13 @@ class ClassWriterMixin(object):
         o_src, o_lab, o_conf, o_text, o_grp = 4, 4 + R, 4 + 2 * R, 4 + 3 * R, 4 + 4 * R
         o_cnt = 4 + 5 * R
         o_void, o_pix, o_flag, o_int = o_cnt + S, o_cnt + 2 * S, o_cnt + 3 * S, o_cnt + 3 * S + fw
-        out = torch.empty((o_int + S * G0,), dtype=torch.int32, device=dev)
+        o_band = o_int + S * G0                                           # the band tables, after everything else
+        if boundary is not None:
+            from ...detectors import instances
+            from ..evaluation import boundary as bd
+            band_d = boundary.band_width(H, W)
+        out = torch.empty((o_band + (bd.table_words(S, G0) if boundary is not None else 0),), dtype=torch.int32,
+                          device=dev)
         poly = torch.empty((R, N, 2), dtype=torch.int32, device=dev)
         masks = torch.empty((S, H, W), dtype=torch.uint8, device=dev)
         at = lambda o: ctypes.c_void_p(out.data_ptr() + 4 * o)            # noqa: E731
@@ -440,6 +467,9 @@ class ClassWriterMixin(object):
         _C.check(L.cp_instance_overlaps(_C.ptr(masks), S, _C.ptr(gt_dev), H, W, _C.ptr(ids), G0,
                                         ctypes.c_void_p(ids.data_ptr() + 4 * G0), len(proto.void_ids), at(o_int),
                                         at(o_void), at(o_pix), _C.ptr(ws), nbytes, st), "cp_instance_overlaps")
+        if boundary is not None:
+            bounds = instances.vertex_bounds(poly[:S], instances.MARGIN["class"], (W, H))
+            bd.enqueue_tables(masks, bounds, gt_dev, band_d, ids, G0, out, o_band)
         host = out.cpu().numpy()
         n = int(host[0])
         if n > il.MAX_MASKS:
@@ -460,6 +490,12 @@ class ClassWriterMixin(object):
             pix = host[o_pix:o_pix + n][order].astype(np.int64)
             evaluator.add_counts(gt_table, res["labels"].tolist(), [float(c) for c in res["conf_text"]], pix,
                                  res["void"], res["inter"])
+        if boundary is not None:
+            b_inter, b_pred, b_gt = bd.read_tables(host, o_band, S, G0, n, masks, bounds, gt_dev, band_d, gt_table)
+            res.update(b_inter=b_inter[order], b_pred=b_pred[order], b_gt=b_gt, band_width=band_d)
+            pix = host[o_pix:o_pix + n][order].astype(np.int64)
+            boundary.add_counts(gt_table, res["labels"].tolist(), [float(c) for c in res["conf_text"]], pix,
+                                res["void"], res["inter"], res["b_pred"], b_gt, res["b_inter"])
         return res
 
     def format_and_write_class_masks(self, all_bboxes, save_dir, evaluator=None, gt_files=None, write_files=True):

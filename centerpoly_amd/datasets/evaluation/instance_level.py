@@ -237,6 +237,11 @@ class InstanceLevelEvaluator(object):
                 ap[0, li, oi] = self._class_ap(lab, th)
         return ap
 
+    def _overlaps(self, pred, cols, size, inter, hit):
+        """The overlap of one prediction (its tuple of add_counts) with the ground truths `cols` of its class, of
+        `size` pixels, sharing `inter` pixels, `hit` where inter > 0: the mask IoU.  evaluation/boundary.py overrides it."""
+        return np.where(hit, inter / np.maximum(size + pred[2] - inter, 1).astype(np.float64), 0.0)
+
     def _class_ap(self, lab, th):
         y_true, y_score = [], []
         hard_fn = 0
@@ -250,10 +255,11 @@ class InstanceLevelEvaluator(object):
             have_gt |= bool(real.any())
             have_pred |= bool(mine)
             best = {}                                                       # ground truth -> score it holds
-            for _, conf, pix, void, row in mine:
+            for pred in mine:
+                _, conf, pix, void, row = pred[:5]
                 inter = row[cols]
                 hit = inter > 0
-                iou = np.where(hit, inter / np.maximum(size + pix - inter, 1).astype(np.float64), 0.0)
+                iou = self._overlaps(pred, cols, size, inter, hit)
                 over = hit & (iou > th)
                 for g in np.flatnonzero(over & real):
                     if g in best:

@@ -130,6 +130,13 @@ class opts(object):
                        help="demo.py / test.py: per image <stem>_panoptic.png and one cityscapes_panoptic_val.json in "
                             "COCO panoptic format under <save_dir>/panoptic/, from the detections above --thresh; "
                             "cityscapes only")
+        p.add_argument("--boundary", action="store_true",
+                       help="test.py: also score the masks by Boundary IoU on the GPU: Boundary AP per class (the AP "
+                            "protocol on min(mask IoU, boundary IoU)) beside the plain AP; needs --gt_dir; cityscapes, "
+                            "kitti_poly and IDD")
+        p.add_argument("--boundary_ratio", type=float, default=0.005,
+                       help="--boundary: the band's width as a share of the image diagonal, d = max(1, round(ratio * "
+                            "diagonal)), 11 pixels at 2048 x 1024 (0.02 is usual for COCO-sized images); d <= 64")
         p.add_argument("--not_prefetch_test", action="store_true")
         p.add_argument("--test_batch_size", type=int, default=1,
                        help="test.py: images per network launch (detector.run_batch); 1 keeps the per-image loop. "
@@ -196,6 +203,20 @@ class opts(object):
             if not opt.gt_dir:
                 self.parser.error("--panoptic needs --gt_dir: the instance maps are scored against the instance-id "
                                   "ground truth found there")
+        if opt.boundary:
+            import math
+
+            from .datasets.evaluation import boundary
+            if opt.dataset not in boundary.DATASETS:
+                self.parser.error("--boundary scores %s only; dataset %r is refused: %s"
+                                  % (", ".join(boundary.DATASETS), opt.dataset,
+                                     "the synthetic set has no ground truth to score against" if opt.dataset == "synthetic"
+                                     else "it has no instance-level AP protocol here"))
+            if not opt.gt_dir:
+                self.parser.error("--boundary needs --gt_dir: the masks are scored against the instance-id ground "
+                                  "truth found there")
+            if not (math.isfinite(opt.boundary_ratio) and opt.boundary_ratio > 0):
+                self.parser.error("--boundary_ratio must be finite and > 0 (got %r)" % opt.boundary_ratio)
         if opt.save_panoptic and opt.dataset != "cityscapes":
             self.parser.error("--save_panoptic writes %s only; dataset %r is refused: %s"
                               % ("cityscapes", opt.dataset,

@@ -55,7 +55,8 @@ extern "C" {
                               cp_render_overlay, cp_render_heatmap, cp_soft_nms_device, cp_merge_detections(_workspace_bytes),
                               cp_dcn_v2_forward_slices(_count), cp_dcn_splitk_reduce, cp_depthwise_up_forward_slices,
                               cp_conv1x1_stream_*, cp_conv3x3_stream_*, cp_instance_map(_workspace_bytes),
-                              cp_pixel_confusion(_workspace_bytes), cp_panoptic_pairs(_workspace_bytes), cp_panoptic_match */
+                              cp_pixel_confusion(_workspace_bytes), cp_panoptic_pairs(_workspace_bytes), cp_panoptic_match,
+                              cp_boundary_overlaps(_workspace_bytes) */
 
 enum {
   CP_OK = 0,
@@ -686,6 +687,43 @@ int cp_panoptic_pairs(const uint8_t* index, int32_t n, const uint16_t* gt_ids, i
                       void* workspace, size_t workspace_bytes, void* stream);
 int cp_panoptic_match(const int32_t* seg, const int32_t* pairs, int32_t n, const int32_t* pred_label, int32_t L,
                       const uint8_t* label_flags, int64_t* stat, double* iou, int32_t* bad, int32_t* match, void* stream);
+
+/* ------------------------------------------------ boundary evaluation (evaluation/boundary.py) --
+ * cp_boundary_overlaps: the pixel counting of Boundary IoU / Boundary AP (Cheng et al., CVPR 2021) for ONE image --
+ * the boundary band of every predicted mask and of every ground-truth value, and their pair counts.  Not in the
+ * reference tree: a capability of this library, defined here and pinned by the host statement
+ * tests/golden/boundary_host.py.
+ * For a set M of pixels of the H x W image and an integer d >= 1,
+ *   band(M, d) = { p in M : some q with max(|qx - px|, |qy - py|) <= d lies outside the image or not in M }
+ * -- what the published implementation computes with one ring of zeros around the mask, d erosions by the 3 x 3
+ * square and `mask - eroded`; a pixel closer than d to the image edge is always in the band.  Integer and exact.
+ *   masks     DEVICE uint8 [n][H][W], non-zero = inside      gt_ids   DEVICE uint16 [H][W]
+ *   bounds    DEVICE int32 [n][4] inclusive x0, y0, x1, y1, or NULL: as cp_instance_map takes them -- mask i is its
+ *             non-zero pixels inside bounds[i] clipped to the image (NULL: the whole image; x1 < x0 or y1 < y0:
+ *             nothing); pixels outside are ignored in every code path alike
+ *   inst_ids  DEVICE int32 [G], distinct values of interest (values outside 16 bits match no pixel)
+ *   d         the band's width in pixels; the caller computes max(1, round(ratio * sqrt(H * H + W * W)))
+ * The ground-truth set of value v is { p : gt_ids[p] == v }, for EVERY value of the image, of interest or not (stuff
+ * and void regions delimit their neighbours), so one band image holds all ground-truth bands: p is in it iff its
+ * (2d + 1)^2 window leaves the image or holds another value.  Outputs (zeroed by the call):
+ *   b_pred   DEVICE int32 [n]:    |band(mask_i, d)|
+ *   b_gt     DEVICE int32 [G]:    band pixels of value inst_ids[j]
+ *   b_inter  DEVICE int32 [n][G]: pixels of band(mask_i, d) that are in the ground-truth band and have
+ *            gt_ids == inst_ids[j]
+ *   pred_bands DEVICE uint8 [n][H][W] or NULL (not written), gt_band DEVICE uint8 [H][W] or NULL (not written): the
+ *            bands as 255 / 0, as cp_instance_masks writes masks; for tests and debug pictures
+ * 0 <= n <= 128, 0 <= G <= 1024, 1 <= d <= 64, H * W < 2^31: beyond the upper limits CP_EUNSUPPORTED; H, W < 1, d < 1,
+ * negative n or G and a null required pointer (gt_ids always; masks and b_pred when n > 0; inst_ids and b_gt when
+ * G > 0; b_inter when both) CP_EINVAL; workspace: cp_boundary_overlaps_workspace_bytes (the id -> column table and the
+ * bit images of the separable erosion: 128 KiB + (4 + 2n) * H * ceil(W / 32) * 4 bytes), shorter or NULL:
+ * CP_EWORKSPACE.  All checks come before any device work.  Any H, W and any alignment of masks.  With n == 0 the
+ * ground-truth side is still computed.  Five launches (three when n == 0; one more fill when pred_bands and bounds are
+ * both given), whatever n, G and d are; integer results, the same bits on every run. */
+size_t cp_boundary_overlaps_workspace_bytes(int32_t n, int32_t G, int32_t H, int32_t W, int32_t d);
+int cp_boundary_overlaps(const uint8_t* masks, int32_t n, const int32_t* bounds, const uint16_t* gt_ids, int32_t H,
+                         int32_t W, int32_t d, const int32_t* inst_ids, int32_t G, int32_t* b_inter, int32_t* b_pred,
+                         int32_t* b_gt, uint8_t* pred_bands, uint8_t* gt_band, void* workspace, size_t workspace_bytes,
+                         void* stream);
 
 /* ------------------------------------------------ training annotations (make_annotations.py) --
  * The "regular interval" recipe of the reference's offline annotation tools (KITTIPolyStuff/Tools/

@@ -11,7 +11,9 @@ the device (evaluation/pixel_level.py): the class and category tables follow the
 resultPixelLevelSemanticLabeling.json is written to save_dir and run_test's dict gains "pixel".  With --panoptic (and
 --gt_dir, cityscapes) the maps are scored as a panoptic segmentation on the device (evaluation/panoptic.py): the PQ
 table follows, resultPanopticSemanticLabeling.json is written and the dict gains "panoptic"; --save_panoptic writes
-the maps in COCO panoptic format under `<save_dir>/panoptic/`.  `--dataset synthetic`
+the maps in COCO panoptic format under `<save_dir>/panoptic/`.  With --boundary (and --gt_dir; cityscapes, kitti_poly,
+IDD) the masks drawn for the AP also go through cp_boundary_overlaps (evaluation/boundary.py): the Boundary AP table
+follows the AP table, resultBoundaryInstanceLevel.json is written and the dict gains "boundary".  `--dataset synthetic`
 feeds hash-generated uint8 arrays (no files)."""
 import os
 import sys
@@ -106,6 +108,12 @@ def run_test(opt, evaluate=True):
             raise ValueError("--pixel_iou needs --gt_dir and a data set with a pixel-level protocol (cityscapes, "
                              "kitti_poly)")
         pixel = pixel_level.PixelLevelEvaluator(pixel_level.PROTOCOLS[pixel_level.DATASET_PROTOCOL[opt.dataset]])
+    bnd = None
+    if getattr(opt, "boundary", False):
+        from centerpoly_amd.datasets.evaluation import boundary
+        if evaluator is None:
+            raise ValueError("--boundary needs --gt_dir and a data set with an AP protocol (cityscapes, kitti_poly, IDD)")
+        bnd = boundary.BoundaryEvaluator(protocol, opt.boundary_ratio)
     images = eval_images.EvalImages(dataset, gt_files, protocol)
     stamps = [time.time()]
     ind = -1
@@ -115,8 +123,12 @@ def run_test(opt, evaluate=True):
             ind += 1
             results[item["img_id"]] = res
             if evaluator is not None:
-                dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"], item["gt_table"],
-                                               evaluator)
+                if bnd is None:
+                    dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"],
+                                                   item["gt_table"], evaluator)
+                else:                                                      # the same masks, the band tables in the same read
+                    dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"],
+                                                   item["gt_table"], evaluator, boundary=bnd)
             if save_ids or save_masks or pixel is not None or pan is not None or save_pan:
                 file_name = dataset.coco.loadImgs(ids=[item["img_id"]])[0]["file_name"]
                 maps = detector.instances(res, image=b)                    # once for the files and the score
@@ -139,6 +151,10 @@ def run_test(opt, evaluate=True):
     else:
         ap = dataset.finish_scored_eval(results, opt.save_dir, evaluator)
     out = {"ap": ap, "results": results, "dataset": dataset, "stamps": stamps}
+    if bnd is not None and evaluate:
+        out["boundary"] = bnd.summarize()
+        print(boundary.format_results(out["boundary"], protocol))
+        boundary.write_results(out["boundary"], opt.save_dir, protocol)
     if pixel is not None and evaluate:
         out["pixel"] = pixel.summarize()
         print(pixel_level.format_results(out["pixel"], pixel.protocol))
