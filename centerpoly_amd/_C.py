@@ -178,6 +178,11 @@ _SIGNATURES = {
     "cp_soft_nms_device": (c_int32, [_P, c_int32, _P, _P, c_int32, c_float, c_float, c_float, c_int32, _P, _P]),
     "cp_merge_detections_workspace_bytes": (c_size_t, [c_int32] * 4),
     "cp_merge_detections": (c_int32, [_P] + [c_int32] * 6 + [c_float] * 3 + [c_int32, _P, _P, _P, c_size_t, _P]),
+    "cp_polygon_overlaps_workspace_bytes": (c_size_t, [c_int32] * 4),
+    "cp_polygon_overlaps": (c_int32, [_P] + [c_int32] * 5 + [_P, _P, _P, c_size_t, _P]),
+    "cp_merge_detections_mask_workspace_bytes": (c_size_t, [c_int32] * 6),
+    "cp_merge_detections_mask": (c_int32, [_P] + [c_int32] * 6 + [c_float] * 3 + [c_int32] * 3 + [_P, _P, _P, c_size_t,
+                                                                                                  _P]),
     "cp_polydet_decode_workspace_bytes": (c_size_t, [c_int32] * 5),
     "cp_polydet_decode": (c_int32, [_P, _P, _P, _P] + [c_int32] * 7 + [_P, _P, _P, _P, c_size_t, _P]),
     "cp_polydet_decode_ex": (c_int32, [_P, _P, _P, _P] + [c_int32] * 8 + [_P, _P, _P, _P, c_size_t, _P]),

@@ -4,7 +4,7 @@ import time
 import numpy as np
 import torch
 
-from ..external.nms import soft_nms
+from ..external.nms import MASK_NMS_METHODS, soft_nms
 from ..models.decode import polydet_decode
 from ..models.utils import flip_tensor
 from .. import _C
@@ -23,8 +23,20 @@ class PolydetDetector(BaseDetector):
     _slot, _merged = 0, False
     _batch = None                                    # the last run_batch's per-image rows and results (None after run)
 
+    # --mask_nms: the scales always stay on the device and merge_outputs_device calls cp_merge_detections_mask (whole
+    # rows, per class, by the IoU of the polygons' masks on the image's canvas) instead of the literal merge; there is no
+    # host path for it, and device_merge does not apply.
+    mask_nms = False                                 # set by the constructor
+    _mask_ws = None                                  # ... its workspace, kept from image to image
+
     def __init__(self, opt):
+        # --mask_nms has no host merge to fall back to: its limits are checked before anything is built
+        if getattr(opt, "mask_nms", False) and (len(opt.test_scales) * opt.K > 1024 or opt.num_classes > 64):
+            raise ValueError("--mask_nms merges at most 1024 rows of at most 64 classes on the device: %d scales x "
+                             "K = %d give %d rows, num_classes = %d"
+                             % (len(opt.test_scales), opt.K, len(opt.test_scales) * opt.K, opt.num_classes))
         super(PolydetDetector, self).__init__(opt)
+        self.mask_nms = bool(getattr(opt, "mask_nms", False))
 
     def process(self, images, return_time=False):
         with torch.no_grad():
@@ -61,7 +73,10 @@ class PolydetDetector(BaseDetector):
 
     def _merge_on_device(self, K):
         """Several scales or --nms (the settings in which merge_outputs does real work), the switch on and the rows
-        within the limits of cp_merge_detections; beyond them merge_outputs on the host remains."""
+        within the limits of cp_merge_detections; beyond them merge_outputs on the host remains.  --mask_nms: always
+        (one scale included; the constructor has checked its limits)."""
+        if self.mask_nms:
+            return True
         return (self.device_merge and (len(self.scales) > 1 or self.opt.nms)
                 and len(self.scales) * K <= 4096 and self.num_classes <= 64)
 
@@ -201,8 +216,8 @@ class PolydetDetector(BaseDetector):
         where post_process_batch left the scales on the device, merge_outputs on the host otherwise."""
         if self._slot > 0:
             kept = {"rows_dev": [], "rows_host": [], "results": []}
-            for rows in self.scale_rows:
-                kept["results"].append(self.merge_outputs_device(rows))
+            for b, rows in enumerate(self.scale_rows):
+                kept["results"].append(self.merge_outputs_device(rows, image=b))
                 kept["rows_dev"].append(self.rows_dev)
                 kept["rows_host"].append(self.rows_host)
             self._batch = kept
@@ -213,21 +228,36 @@ class PolydetDetector(BaseDetector):
         self._batch["results"] = results
         return results
 
-    def merge_outputs_device(self, rows=None):
+    def merge_outputs_device(self, rows=None, image=0):
         """merge_outputs on the rows post_process left on the device (cp_merge_detections: the class split, soft-nms
         and the max_per_image cut, literal behaviour), then ONE device -> host copy of the table and its counts, from
         which the `results` of run() are cut: the same keys, shapes and bits as merge_outputs gives.  The table stays
-        on the device for device_rows.  `rows`: one image's [S, K, ncols] slice of a batch (merge_batch)."""
+        on the device for device_rows.  `rows`: one image's [S, K, ncols] slice of a batch (merge_batch).
+        --mask_nms: cp_merge_detections_mask instead, on the canvas of image `image` (self.image_sizes): whole rows,
+        per class, by the IoU of the polygons' masks (--mask_nms_method; sigma 0.5, Nt 0.5, threshold 0.001)."""
         rows, C = self.scale_rows if rows is None else rows, self.num_classes
         S, K, ncols = rows.shape
         self._slot = 0
         lib = _C.lib()
-        ws = _C.workspace(lib.cp_merge_detections_workspace_bytes(S, K, ncols, C), rows.device)
         blob = torch.empty(S * K * ncols + 1 + C, dtype=torch.float32, device=rows.device)    # the table, then the counts
         out, counts = blob[:S * K * ncols].view(S * K, ncols), blob[S * K * ncols:].view(torch.int32)
-        _C.check(lib.cp_merge_detections(_C.ptr(rows), S, K, ncols, C, self.max_per_image, 1, 0.5, 0.5, 0.001, 2,
-                                         _C.ptr(out), _C.ptr(counts), _C.ptr(ws), ws.numel(), _C.stream()),
-                 "cp_merge_detections")
+        if self.mask_nms:
+            W, H = self.image_sizes[image]
+            need = lib.cp_merge_detections_mask_workspace_bytes(S, K, ncols, C, H, W)
+            if need == 0:
+                raise ValueError("--mask_nms cannot merge rows [%d, %d, %d] of %d classes on a %d x %d canvas"
+                                 % (S, K, ncols, C, W, H))
+            if self._mask_ws is None or self._mask_ws.numel() < need or self._mask_ws.device != rows.device:
+                self._mask_ws = _C.workspace(need, rows.device)
+            _C.check(lib.cp_merge_detections_mask(_C.ptr(rows), S, K, ncols, C, self.max_per_image, 1, 0.5, 0.5, 0.001,
+                                                  MASK_NMS_METHODS[getattr(self.opt, "mask_nms_method", "gaussian")],
+                                                  H, W, _C.ptr(out), _C.ptr(counts), _C.ptr(self._mask_ws),
+                                                  self._mask_ws.numel(), _C.stream()), "cp_merge_detections_mask")
+        else:
+            ws = _C.workspace(lib.cp_merge_detections_workspace_bytes(S, K, ncols, C), rows.device)
+            _C.check(lib.cp_merge_detections(_C.ptr(rows), S, K, ncols, C, self.max_per_image, 1, 0.5, 0.5, 0.001, 2,
+                                             _C.ptr(out), _C.ptr(counts), _C.ptr(ws), ws.numel(), _C.stream()),
+                     "cp_merge_detections")
         host = blob.cpu().numpy()
         n = host[S * K * ncols:].view(np.int32)
         table = host[:int(n[0]) * ncols].reshape(-1, ncols)

@@ -103,6 +103,15 @@ class opts(object):
         p.add_argument("--flip_test", action="store_true")
         p.add_argument("--test_scales", type=str, default="1")
         p.add_argument("--nms", action="store_true")
+        p.add_argument("--mask_nms", action="store_true",
+                       help="merge the test scales by a whole-row, per-class soft-NMS whose overlap is the IoU of the "
+                            "polygons' masks, on the GPU (cp_merge_detections_mask): every output row is one detection "
+                            "with its own polygon and depth.  Replaces the reference's literal merge of --nms / "
+                            "--test_scales a,b, which moves boxes and scores only; implies the merge at one scale too "
+                            "and wins over --nms.  At most 1024 rows (scales x K) and 64 classes")
+        p.add_argument("--mask_nms_method", default="gaussian", choices=["gaussian", "linear", "hard"],
+                       help="--mask_nms: the decay of a row that overlaps a selected one: exp(-ov^2 / 0.5), 1 - ov above "
+                            "0.5, or removal above 0.5")
         p.add_argument("--K", type=int, default=128)
         p.add_argument("--thresh", type=float, default=0.05,
                        help="threshold for the outputs kept for evaluation (result writer)")

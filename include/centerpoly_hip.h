@@ -56,7 +56,8 @@ extern "C" {
                               cp_dcn_v2_forward_slices(_count), cp_dcn_splitk_reduce, cp_depthwise_up_forward_slices,
                               cp_conv1x1_stream_*, cp_conv3x3_stream_*, cp_instance_map(_workspace_bytes),
                               cp_pixel_confusion(_workspace_bytes), cp_panoptic_pairs(_workspace_bytes), cp_panoptic_match,
-                              cp_boundary_overlaps(_workspace_bytes) */
+                              cp_boundary_overlaps(_workspace_bytes), cp_polygon_overlaps(_workspace_bytes),
+                              cp_merge_detections_mask(_workspace_bytes) */
 
 enum {
   CP_OK = 0,
@@ -998,6 +999,65 @@ size_t cp_merge_detections_workspace_bytes(int32_t S, int32_t K, int32_t ncols, 
 int cp_merge_detections(const float* rows, int32_t S, int32_t K, int32_t ncols, int32_t num_classes,
                         int32_t max_per_image, int32_t nms, float sigma, float Nt, float threshold, int32_t method,
                         float* out, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------ mask NMS (--mask_nms) --
+ * The merge above is the reference's, literally: after it a box and its score sit in a row whose polygon and depth
+ * belong to another detection, and the overlap that drives the decay is the box IoU.  The two entry points below
+ * (csrc/mask_nms.hip) are the merge whose output can be used.  The definition is this project's own, not the
+ * reference's:
+ *   candidates  the rows [S][K][ncols] of all scales, scale by scale and row by row, ncols = 2 N + 7
+ *               (x1,y1,x2,y2,score,cls,poly(2N),depth); a row takes part when its class equals an integer of
+ *               [0, num_classes), the rule of cp_merge_detections.  A row's POSITION is its index in that order within
+ *               its class.
+ *   mask        F of a row: the pixels ImageDraw.polygon(pts, fill=1) sets on an H x W 'L' image (PIL's scan-line
+ *               fill: csrc/class_masks_core.h, fitted against PIL 12.2), the vertices int(float("%.2f" % v)) as the
+ *               result writers use, clipped to the canvas; no outline pass, no dilation, no occlusion, the same for
+ *               every data set.
+ *   overlap     of two candidates of one class: inter = |F_i & F_j|, uni = |F_i| + |F_j| - inter,
+ *               ov = (double)inter / (double)uni, 0 when uni == 0.
+ *   selection   per class: take the live candidate with the largest score, the lowest position on a tie; if its score
+ *               is below `threshold` the class stops and all its remaining rows are dropped; otherwise it moves to the
+ *               output and every remaining live candidate p decays once, score_p = (float)(w * (double)score_p) with w
+ *               in double: method 0 (hard) w = ov > Nt ? 0 : 1; 1 (linear) w = ov > Nt ? 1 - ov : 1; 2 (gaussian)
+ *               w = exp(-(ov * ov) / sigma) (the device library's double exp).  A pair with inter == 0 is left
+ *               untouched.
+ *   cut         merge_outputs' rule on the kept rows of all classes: with more than max_per_image of them, those with
+ *               score >= the (total - max_per_image)-th smallest stay (ties are kept).
+ *   output      the layout of cp_merge_detections: out[0 : counts[0]] class by class, counts [1 + num_classes]; within
+ *               a class the rows in selection order.  Every column of a row is copied from its ONE source row, except
+ *               that column 4 holds the final score.  There are no stale slots; rows beyond counts[0] are not
+ *               specified.  Scores are assumed finite: with a NaN score the call terminates inside its buffers and its
+ *               result is unspecified.
+ *
+ * cp_polygon_overlaps: the masks' pixel counts of R DEVICE rows [R][ncols] on an H x W canvas.
+ *   area   DEVICE int32 [R]: |F_i| (0 for a row without a class)
+ *   inter  DEVICE int32 [R][R]: |F_i & F_j|; inter[i][i] == area[i], the matrix is symmetric, and it holds 0 for pairs
+ *          of different class and for rows without a class.  Integers: a call repeats its bits.
+ * Two memsets and three launches: the classes and the clipped boxes (one workgroup), the raster (one wave per row and
+ * image row, the spans ORed into a bit plane per candidate of ceil(W / 32) words a row, only the words of the
+ * candidate's own box written), the pairs (one wave per pair of one class whose boxes intersect: popcount(A & B) over
+ * the intersection of the boxes).  Workspace: R bit planes plus tables, cp_polygon_overlaps_workspace_bytes(R, ncols,
+ * H, W) (0 for a refused shape); 16-byte aligned.
+ *
+ * cp_merge_detections_mask: the signature of cp_merge_detections plus the canvas H, W.  The class split, the overlaps,
+ * the selection (one wave per class) and the cut: one memset and five launches whatever S * K is, nothing allocated.
+ * With nms == 0 no mask is drawn and no row decays or is dropped: each class by descending score, then the cut.
+ * Workspace: the planes, the matrix and tables, cp_merge_detections_mask_workspace_bytes(S, K, ncols, num_classes, H,
+ * W) -- 64 MiB at S * K = 256 on 2048 x 1024, 256 MiB at 1024 rows; only box-sized parts of the planes are touched.
+ *
+ * Both: R = S * K <= 1024, N = (ncols - 7) / 2 <= 64, num_classes <= 64, H * W < 2^31, otherwise CP_EUNSUPPORTED; null
+ * pointers, non-positive sizes, ncols even or below 13 (N < 3), max_per_image < 1, a method outside 0..2, out == rows,
+ * a workspace that is not 16-byte aligned: CP_EINVAL; a short workspace: CP_EWORKSPACE.  All checks come before any
+ * device work. */
+size_t cp_polygon_overlaps_workspace_bytes(int32_t R, int32_t ncols, int32_t H, int32_t W);
+int cp_polygon_overlaps(const float* rows, int32_t R, int32_t ncols, int32_t num_classes, int32_t H, int32_t W,
+                        int32_t* area, int32_t* inter, void* workspace, size_t workspace_bytes, void* stream);
+size_t cp_merge_detections_mask_workspace_bytes(int32_t S, int32_t K, int32_t ncols, int32_t num_classes, int32_t H,
+                                                int32_t W);
+int cp_merge_detections_mask(const float* rows, int32_t S, int32_t K, int32_t ncols, int32_t num_classes,
+                             int32_t max_per_image, int32_t nms, float sigma, float Nt, float threshold, int32_t method,
+                             int32_t H, int32_t W, float* out, int32_t* counts, void* workspace, size_t workspace_bytes,
+                             void* stream);
 
 /* ------------------------------------------------- training-target construction --
  * The per-object loop of PolydetDataset.__getitem__ (src/lib/datasets/sample/polydet.py:160-405)
