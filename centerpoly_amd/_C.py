@@ -108,6 +108,8 @@ _SIGNATURES = {
     "cp_instance_overlaps_workspace_bytes": (c_size_t, [c_int32] * 4),
     "cp_instance_overlaps": (c_int32, [_P, c_int32, _P, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, _P,
                                        c_size_t, _P]),
+    "cp_segment_medians_workspace_bytes": (c_size_t, [c_int32] * 3),
+    "cp_segment_medians": (c_int32, [_P, _P, c_int32, c_int32, _P, c_int32, _P, _P, c_size_t, _P]),
     "cp_instance_map_workspace_bytes": (c_size_t, [c_int32] * 3),
     "cp_instance_map": (c_int32, [_P, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int32, _P, _P, _P, c_int32, c_int32,
                                   _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),

@@ -107,10 +107,11 @@ class PolygonDataset(data.Dataset):
         return 0.0
 
     def report_eval(self, evaluator, res_dir):
-        """The evaluator's table on the screen, its JSON below res_dir; returns allAp."""
+        """The evaluator's table on the screen, its JSON below res_dir; returns allAp (the whole dictionary stays in
+        last_summary: with distances it holds allAp100m, allAp50m and allAp50%50m too)."""
         from ..evaluation import instance_level
         self.last_evaluator = evaluator
-        res = evaluator.summarize()
+        res = self.last_summary = evaluator.summarize()
         print(instance_level.format_results(res, evaluator.protocol))
         out_dir = os.path.join(res_dir, "evaluationResults")
         os.makedirs(out_dir, exist_ok=True)
@@ -183,7 +184,7 @@ class CityscapesWriterMixin(object):
         names = cls.class_name[1:]
         return np.array([[cls.label_to_id[c], 0 if c in cls.no_mask_labels else 1] for c in names], np.int32)
 
-    def score_instances_device(self, rows_dev, gt_ids, gt_table=None, evaluator=None, boundary=None):
+    def score_instances_device(self, rows_dev, gt_ids, gt_table=None, evaluator=None, boundary=None, distances=None):
         """One image scored from its detection rows without a pass through host Python: device float32 rows
         [R, 2N + 7] in the layout cp_polydet_post_process writes (x1,y1,x2,y2,score,cls,poly,depth; R <= 1024)
         -> cp_writer_instances -> cp_instance_masks -> cp_instance_overlaps on all slots, then ONE read of the small
@@ -194,7 +195,11 @@ class CityscapesWriterMixin(object):
         n, src, labels, conf (float32), conf_text, counts, kept, gt_table, inter, void.
         boundary: an evaluation.boundary.BoundaryEvaluator, or None.  With one, the masks also go through
         cp_boundary_overlaps (bounds: the polygons' boxes grown by the writer's radius-2 dilation); the band tables come
-        back in the same read, are returned as b_inter, b_pred, b_gt and band_width, and the kept rows are added to it."""
+        back in the same read, are returned as b_inter, b_pred, b_gt and band_width, and the kept rows are added to it.
+        distances: (disparity, camera) of the image -- a host uint16 [H, W] array or a device tensor of 16-bit elements,
+        and (baseline, fx) -- or None.  With it the ground-truth table's ids go through cp_segment_medians on the id
+        image (evaluation/distances.py); the integers come back in the same read, the [G, 2] table (medDist, distConf)
+        is returned as gt_dist (gt_dist_raw: the integers) and goes to the evaluators as add_counts' gt_dist."""
         import ctypes
 
         import torch
@@ -228,8 +233,8 @@ class CityscapesWriterMixin(object):
             from ...detectors import instances
             from ..evaluation import boundary as bd
             band_d = boundary.band_width(H, W)
-        out = torch.empty((o_band + (bd.table_words(S, G0) if boundary is not None else 0),), dtype=torch.int32,
-                          device=dev)
+        o_med = o_band + (bd.table_words(S, G0) if boundary is not None else 0)   # the median integers, last
+        out = torch.empty((o_med + (4 * G0 if distances is not None else 0),), dtype=torch.int32, device=dev)
         o_src, o_lab, o_conf = 4, 4 + R, 4 + 2 * R
         o_cnt = 4 + 3 * R
         o_void, o_pix, o_flag, o_int = o_cnt + S, o_cnt + 2 * S, o_cnt + 3 * S, o_cnt + 3 * S + fw
@@ -250,6 +255,11 @@ class CityscapesWriterMixin(object):
         if boundary is not None:
             bounds = instances.vertex_bounds(poly[:S], instances.MARGIN["cityscapes"], (W, H))
             bd.enqueue_tables(masks, bounds, gt_dev, band_d, ids, G0, out, o_band)
+        if distances is not None:
+            from ..evaluation import distances as dist
+            disp_dev = il.device_ids(distances[0], dev, "disparity")
+            if G0:
+                dist.enqueue_medians(gt_dev, disp_dev, ids, G0, out[o_med:])
         host = out.cpu().numpy()
         n = int(host[0])
         if n > il.MAX_MASKS:
@@ -268,21 +278,31 @@ class CityscapesWriterMixin(object):
         kept = [k for k in range(n) if flags[k] & 1 and counts[k] > 100]
         res["kept"] = kept
         res["conf_text"] = [str(min(1, conf[k])) for k in kept]
+        extra = {}
+        if distances is not None:
+            raw = host[o_med:o_med + 4 * G0].reshape(G0, 4).astype(np.int64)
+            if G > G0:                                                    # more ids than one call takes: rare
+                raw = np.concatenate([raw, dist.instance_distances(gt_dev, gt_table[G0:, 0], disp_dev, distances[1])[1]])
+            res["gt_dist_raw"] = raw
+            res["gt_dist"] = dist.table_from_counts(raw, distances[1])
+            extra = {"gt_dist": res["gt_dist"]}
         if evaluator is not None:
             pix = host[o_pix:o_pix + n].astype(np.int64)
             evaluator.add_counts(gt_table, res["labels"][kept].tolist(), [float(c) for c in res["conf_text"]],
-                                 pix[kept], res["void"][kept], inter[kept])
+                                 pix[kept], res["void"][kept], inter[kept], **extra)
         if boundary is not None:
             b_inter, b_pred, b_gt = bd.read_tables(host, o_band, S, G0, n, masks, bounds, gt_dev, band_d, gt_table)
             res.update(b_inter=b_inter, b_pred=b_pred, b_gt=b_gt, band_width=band_d)
             pix = host[o_pix:o_pix + n].astype(np.int64)
             boundary.add_counts(gt_table, res["labels"][kept].tolist(), [float(c) for c in res["conf_text"]],
-                                pix[kept], res["void"][kept], inter[kept], b_pred[kept], b_gt, b_inter[kept])
+                                pix[kept], res["void"][kept], inter[kept], b_pred[kept], b_gt, b_inter[kept], **extra)
         return res
 
-    def format_and_write_to_cityscapes(self, all_bboxes, save_dir, evaluator=None, gt_files=None, write_files=True):
+    def format_and_write_to_cityscapes(self, all_bboxes, save_dir, evaluator=None, gt_files=None, write_files=True,
+                                       dist_files=None):
         """Writes the result files; with an `evaluator` (evaluation.instance_level.InstanceLevelEvaluator) the kept
-        masks are also scored against `gt_files` ({image prefix: id image path}) while they are on the device."""
+        masks are also scored against `gt_files` ({image prefix: id image path}) while they are on the device; for an
+        evaluator with distances, dist_files is evaluation.distances.find_files' dictionary."""
         from PIL import Image
         id_to_file = {im["id"]: im["file_name"] for im in self.coco.imgs.values()}
         masks_dir = os.path.join(save_dir, "masks")
@@ -307,8 +327,17 @@ class CityscapesWriterMixin(object):
                     raise ValueError("%s is %s, the result canvas is %s" % (gt_files[prefix], gt_ids.shape,
                                                                             tuple(masks_dev.shape[1:])))
                 sel = masks_dev if len(kept) == len(params) else masks_dev[kept]
+                extra = {}
+                if dist_files is not None:
+                    from ..evaluation import distances
+                    disp_path, cam_path = distances.frame_files(dist_files, prefix, base)
+                    disp = distances.read_disparity(disp_path)
+                    if disp.shape != gt_ids.shape:
+                        raise ValueError("%s is %s, the ground truth %s is %s" % (disp_path, disp.shape,
+                                                                                  gt_files[prefix], gt_ids.shape))
+                    extra = {"disparity": disp, "camera": distances.read_camera(cam_path)}
                 evaluator.add_image(sel, [self.label_to_id[params[k][2]] for k in kept], [float(c) for c in confs],
-                                    gt_ids)
+                                    gt_ids, **extra)
             if not write_files:
                 continue
             masks = masks_dev.cpu().numpy()
@@ -603,9 +632,18 @@ class CITYSCAPES(CityscapesWriterMixin, PolygonDataset):
         from ..evaluation import instance_level
         if not os.path.isdir(gt_dir):
             raise FileNotFoundError("--gt_dir %s is not a directory" % gt_dir)
-        evaluator = instance_level.InstanceLevelEvaluator()
+        dist_files = None
+        if getattr(self.opt, "disparity_dir", "") and getattr(self.opt, "camera_dir", ""):
+            from ..evaluation import distances                             # AP 100 m / AP 50 m beside the AP
+            dist_files = distances.find_files(self.opt.disparity_dir, self.opt.camera_dir)
+            for im in self.coco.imgs.values():                             # a frame without its files: before any score
+                if im["id"] in results or str(im["id"]) in results:
+                    distances.frame_files(dist_files, instance_level.CITYSCAPES.image_key(im["file_name"]),
+                                          os.path.basename(im["file_name"]))
+        evaluator = instance_level.InstanceLevelEvaluator(distances=dist_files is not None)
         self.format_and_write_to_cityscapes(results, res_dir, evaluator, instance_level.find_gt_files(gt_dir),
-                                            write_files=not getattr(self.opt, "no_mask_files", False))
+                                            write_files=not getattr(self.opt, "no_mask_files", False),
+                                            dist_files=dist_files)
         return self.report_eval(evaluator, res_dir)
 
     def finish_scored_eval(self, results, save_dir, evaluator):

@@ -2,7 +2,9 @@
 `coco.loadImgs` -> `read_image`, one item per image.  An item is decoded on the host only, so the items can come from
 `DataLoader` workers while the detector runs: the 8-bit BGR image and, when ground truth is scored, the 16-bit id
 image with its ground-truth table (`gt_instances` on an `np.bincount`, so no histogram has to come back from the
-device before the overlap kernel starts).  A missing image or ground-truth file is an error that names the path."""
+device before the overlap kernel starts).  With --disparity_dir / --camera_dir also the frame's 16-bit disparity image
+and its camera's (baseline, fx), for the distance columns of the AP.  A missing image or ground-truth file is an error
+that names the path; a frame without its disparity or camera file is one when the list is made."""
 import os
 
 import numpy as np
@@ -17,10 +19,14 @@ def image_prefix(file_name):
 
 
 class EvalImages(data.Dataset):
-    def __init__(self, dataset, gt_files=None, protocol=None):
+    def __init__(self, dataset, gt_files=None, protocol=None, dist_files=None):
         self.dataset = dataset
         self.gt_files = gt_files                               # {image key: id image path} or None
         self.protocol = protocol or instance_level.CITYSCAPES  # whose key, ground-truth table and file names
+        self.dist_files = dist_files                           # distances.find_files' dictionary or None
+        if dist_files is not None:                             # a frame without its two files: before anything is scored
+            for ind in range(len(self)):
+                self.distance_paths(self.info(ind)[1])
 
     def __len__(self):
         return len(self.dataset.images)
@@ -37,6 +43,10 @@ class EvalImages(data.Dataset):
                                     % (self.protocol.gt_name(key), os.path.basename(file_name)))
         return self.gt_files[key]
 
+    def distance_paths(self, file_name):
+        from .evaluation import distances
+        return distances.frame_files(self.dist_files, self.protocol.image_key(file_name), os.path.basename(file_name))
+
     def __getitem__(self, ind):
         img_id, file_name = self.info(ind)
         item = {"img_id": img_id, "image": self.dataset.read_image(file_name)}
@@ -51,6 +61,14 @@ class EvalImages(data.Dataset):
             item["gt_ids"] = ids
             item["gt_table"] = instance_level.gt_instances(np.bincount(ids.reshape(-1), minlength=65536),
                                                            self.protocol)
+            if self.dist_files is not None:
+                from .evaluation import distances
+                disp_path, cam_path = self.distance_paths(file_name)
+                disp = distances.read_disparity(disp_path)
+                if disp.shape != ids.shape:
+                    raise ValueError("%s is %s, the ground truth %s is %s" % (disp_path, disp.shape, path, ids.shape))
+                item["disparity"] = disp
+                item["camera"] = distances.read_camera(cam_path)
         return item
 
 

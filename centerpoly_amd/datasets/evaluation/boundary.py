@@ -125,8 +125,8 @@ class BoundaryEvaluator(il.InstanceLevelEvaluator):
     boundary IoU = b_inter / max(b_gt + b_pred - b_inter, 1) for a pair that shares a mask pixel.  Per image it keeps
     the three band tables beside the mask tables, so the same counts give the plain AP too."""
 
-    def __init__(self, protocol=il.CITYSCAPES, ratio=DEFAULT_RATIO):
-        super(BoundaryEvaluator, self).__init__(protocol)
+    def __init__(self, protocol=il.CITYSCAPES, ratio=DEFAULT_RATIO, distances=False):
+        super(BoundaryEvaluator, self).__init__(protocol, distances)
         ratio = float(ratio)
         if not (math.isfinite(ratio) and ratio > 0):
             raise ValueError("the boundary ratio must be finite and > 0, got %r" % ratio)
@@ -141,12 +141,14 @@ class BoundaryEvaluator(il.InstanceLevelEvaluator):
         return d
 
     def add_counts(self, gt_table, label_ids, confidences, pred_pixels, void_inter, inter, b_pred=None, b_gt=None,
-                   b_inter=None):
+                   b_inter=None, gt_dist=None):
         """InstanceLevelEvaluator.add_counts plus the band tables of the image: b_pred [n], b_gt [G] (the band of
-        gt_table[j]'s id), b_inter [n, G]."""
+        gt_table[j]'s id), b_inter [n, G].  gt_dist as InstanceLevelEvaluator.add_counts takes it: with distances the
+        matrix has the three settings (the printed table shows the first)."""
         if b_pred is None or b_gt is None or b_inter is None:
             raise ValueError("BoundaryEvaluator.add_counts needs b_pred, b_gt and b_inter")
         gt_table = np.asarray(gt_table, np.int64).reshape(-1, 3)
+        self._note_distances(gt_table, gt_dist)
         n, G = len(label_ids), len(gt_table)
         inter = np.asarray(inter, np.int64).reshape(n, G)
         b_inter = np.asarray(b_inter, np.int64).reshape(n, G)

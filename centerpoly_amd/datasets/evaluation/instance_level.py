@@ -1,5 +1,7 @@
-"""Instance-level AP of Cityscapes, KITTI and IDD (the protocol of cityscapesscripts' evalInstanceLevelSemanticLabeling, the
-`distanceAvailable = False` case the reference runs after test.py), written from the algorithm.
+"""Instance-level AP of Cityscapes, KITTI and IDD (the protocol of cityscapesscripts' evalInstanceLevelSemanticLabeling),
+written from the algorithm: by default the `distanceAvailable = False` case the reference runs after test.py; with
+`InstanceLevelEvaluator(distances=True)` the evaluator's three settings (all, within 100 m, within 50 m: AP 100 m and
+AP 50 m of the Cityscapes table), from the per-instance distances of evaluation/distances.py.
 
 The pixel work -- one count per (predicted mask, ground-truth instance) pair, the void overlap, the mask sizes and
 the ground-truth table -- is done on the device by cp_instance_overlaps / cp_id_histogram from the masks
@@ -7,7 +9,9 @@ cp_instance_masks leaves there and the 16-bit `*_gtFine_instanceIds.png` image. 
 tables per image and turns them into the AP numbers in float64 on the host.
 
 Per image and per class the protocol holds, for every threshold t in OVERLAPS:
-  * ground truths: ids >= 1000 of the class with at least MIN_REGION_SIZE pixels (ids below 1000 are groups);
+  * ground truths: ids >= 1000 of the class with at least MIN_REGION_SIZE pixels (ids below 1000 are groups); in a
+    distance setting (minRegionSize, distanceTh, distanceConf) also medDist <= distanceTh and distConf >= distanceConf,
+    and an instance outside the setting is ignored like a small one (a group outside it counts twice);
   * a prediction matches a ground truth when IoU = inter / (gt + pred - inter) > t.  The first match of a ground
     truth is a true positive with the prediction's confidence; every further match makes a false positive that
     carries the lower of the two confidences, the ground truth keeping the higher;
@@ -29,6 +33,10 @@ VOID_IDS = (0, 1, 2, 3, 4, 5, 6, 9, 10, 14, 15, 16, 18, 29, 30, -1)
 OVERLAPS = np.arange(0.5, 1.0, 0.05)
 MIN_REGION_SIZES = np.array([100, 1000, 1000])          # only the first is used without distances
 MIN_REGION_SIZE = 100
+# with distances (evaluation/distances.py) the evaluator's three settings: all, within 100 m, within 50 m; a ground
+# truth is real in a setting when medDist <= the bound and distConf (its stereo density) >= the density bound
+DISTANCE_THS = np.array([np.inf, 100.0, 50.0])
+DISTANCE_CONFS = np.array([-np.inf, 0.5, 0.5])
 GT_SUFFIX = "_gtFine_instanceIds.png"
 MAX_MASKS, MAX_INST = 128, 1024                          # limits of cp_instance_overlaps
 
@@ -189,16 +197,44 @@ def device_histogram(gt_dev):
 class InstanceLevelEvaluator(object):
     """Collects the count tables image by image (add_image / add_counts) and scores them (summarize)."""
 
-    def __init__(self, protocol=CITYSCAPES):
+    def __init__(self, protocol=CITYSCAPES, distances=False):
+        """distances: score the evaluator's three settings (all, 100 m, 50 m) instead of the first alone; every image
+        then comes with its [G, 2] table of (medDist, distConf), see evaluation/distances.py."""
         self.protocol = protocol
+        self.distances = bool(distances)
         self.images = []
+        self.gt_dists = []                                                # per image [G, 2], or None without distances
 
-    def add_counts(self, gt_table, label_ids, confidences, pred_pixels, void_inter, inter):
+    def settings(self):
+        """(minRegionSize, distanceTh, distanceConf) of every scored setting: the first alone without distances."""
+        k = len(MIN_REGION_SIZES) if self.distances else 1
+        return list(zip(MIN_REGION_SIZES[:k].tolist(), DISTANCE_THS[:k].tolist(), DISTANCE_CONFS[:k].tolist()))
+
+    def _note_distances(self, gt_table, gt_dist):
+        """The distance table of the image add_counts is about to append, checked against the evaluator's mode."""
+        if gt_dist is None:
+            if self.distances:
+                raise ValueError("this evaluator scores the distance settings: every image needs its gt_dist table "
+                                 "(add_counts(..., gt_dist=), add_image(..., disparity=, camera=))")
+        else:
+            if not self.distances:
+                raise ValueError("a distance table was given to an evaluator made with distances=False")
+            gt_dist = np.asarray(gt_dist, np.float64)
+            if gt_dist.shape != (len(gt_table), 2):
+                raise ValueError("gt_dist is %s, the ground-truth table has %d rows: expected [%d, 2] (medDist, "
+                                 "distConf)" % (gt_dist.shape, len(gt_table), len(gt_table)))
+            if np.isnan(gt_dist).any():
+                raise ValueError("gt_dist holds NaN")
+        self.gt_dists.append(gt_dist)
+
+    def add_counts(self, gt_table, label_ids, confidences, pred_pixels, void_inter, inter, gt_dist=None):
         """One image from its counts: gt_table [G, 3] as gt_instances returns it; per prediction its label id,
         confidence, pixel count and void overlap; inter [n, G], column j counted against gt_table[j].  Predictions
         with a label without instances or without pixels are skipped, as the protocol skips them.  The order of
-        the predictions is the order of the text file's lines: the scores are sorted stably, so it can show in an AP."""
+        the predictions is the order of the text file's lines: the scores are sorted stably, so it can show in an AP.
+        gt_dist: float64 [G, 2] (medDist, distConf) of gt_table's rows, for an evaluator with distances."""
         gt_table = np.asarray(gt_table, np.int64).reshape(-1, 3)
+        self._note_distances(gt_table, gt_dist)
         inter = np.asarray(inter, np.int64).reshape(len(label_ids), len(gt_table))
         preds = []
         for i, (lab, conf) in enumerate(zip(label_ids, confidences)):
@@ -207,10 +243,17 @@ class InstanceLevelEvaluator(object):
             preds.append((int(lab), float(conf), int(pred_pixels[i]), int(void_inter[i]), inter[i]))
         self.images.append((gt_table, preds))
 
-    def add_image(self, masks_dev, label_ids, confidences, gt_ids):
+    def add_image(self, masks_dev, label_ids, confidences, gt_ids, disparity=None, camera=None):
         """One image from device masks uint8 [n, H, W] (any n: the kernel is called on slices of 128) and its id
-        image: a host uint16 [H, W] array, or a device tensor of 16-bit elements holding those bits."""
+        image: a host uint16 [H, W] array, or a device tensor of 16-bit elements holding those bits.  For an evaluator
+        with distances: the image's disparity (host uint16 [H, W] or device tensor) and camera (baseline, fx)."""
         import torch
+        if (disparity is None) != (camera is None):
+            raise ValueError("disparity and camera come together")
+        if (disparity is not None) != self.distances:
+            raise ValueError("this evaluator scores the distance settings: add_image needs disparity and camera"
+                             if self.distances else
+                             "a disparity was given to an evaluator made with distances=False")
         n = int(masks_dev.shape[0])
         # (an image without predictions still has ground truth to count: on the default device)
         gt_ids = device_ids(gt_ids, masks_dev.device if n else torch.device("cuda"))
@@ -227,14 +270,21 @@ class InstanceLevelEvaluator(object):
             for g in range(0, max(G, 1), MAX_INST):
                 i, v, p = device_counts(masks_dev[a:a + MAX_MASKS], gt_ids, table[g:g + MAX_INST, 0], self.protocol)
                 inter[a:a + MAX_MASKS, g:g + MAX_INST], void[a:a + MAX_MASKS], pix[a:a + MAX_MASKS] = i, v, p
-        self.add_counts(table, label_ids, confidences, pix, void, inter)
+        gt_dist = None
+        if disparity is not None:
+            from . import distances
+            gt_dist = distances.instance_distances(gt_ids, table[:, 0], disparity, camera)[0]
+        self.add_counts(table, label_ids, confidences, pix, void, inter, gt_dist=gt_dist)
 
     def ap_matrix(self):
-        """float64 [1, labels, 10]: AP per (region size setting, class, overlap threshold)."""
-        ap = np.zeros((1, len(self.protocol.label_ids), len(OVERLAPS)), np.float64)
-        for oi, th in enumerate(OVERLAPS):
-            for li, lab in enumerate(self.protocol.label_ids):
-                ap[0, li, oi] = self._class_ap(lab, th)
+        """float64 [settings, labels, 10]: AP per (setting, class, overlap threshold); one setting without
+        distances, three (all, 100 m, 50 m) with them."""
+        settings = self.settings()
+        ap = np.zeros((len(settings), len(self.protocol.label_ids), len(OVERLAPS)), np.float64)
+        for di, setting in enumerate(settings):
+            for oi, th in enumerate(OVERLAPS):
+                for li, lab in enumerate(self.protocol.label_ids):
+                    ap[di, li, oi] = self._class_ap(lab, th, setting)
         return ap
 
     def _overlaps(self, pred, cols, size, inter, hit):
@@ -242,15 +292,19 @@ class InstanceLevelEvaluator(object):
         `size` pixels, sharing `inter` pixels, `hit` where inter > 0: the mask IoU.  evaluation/boundary.py overrides it."""
         return np.where(hit, inter / np.maximum(size + pred[2] - inter, 1).astype(np.float64), 0.0)
 
-    def _class_ap(self, lab, th):
+    def _class_ap(self, lab, th, setting=(MIN_REGION_SIZE, np.inf, -np.inf)):
+        min_size, dist_th, dist_conf = setting
         y_true, y_score = [], []
         hard_fn = 0
         have_gt = have_pred = False
-        for table, preds in self.images:
+        for (table, preds), gt_dist in zip(self.images, self.gt_dists):
             cols = np.flatnonzero(table[:, 1] == lab)                      # every id of the class, groups included
             ids, size = table[cols, 0], table[cols, 2]
-            real = (ids >= 1000) & (size >= MIN_REGION_SIZE)
-            ignore = (ids < 1000).astype(np.int64) + (size < MIN_REGION_SIZE)   # a small group counts twice
+            out = size < min_size                                          # outside the setting: small, far or sparse
+            if gt_dist is not None:
+                out = out | (gt_dist[cols, 0] > dist_th) | (gt_dist[cols, 1] < dist_conf)
+            real = (ids >= 1000) & ~out
+            ignore = (ids < 1000).astype(np.int64) + out                    # a small group counts twice
             mine = [p for p in preds if p[0] == lab]
             have_gt |= bool(real.any())
             have_pred |= bool(mine)
@@ -299,26 +353,61 @@ class InstanceLevelEvaluator(object):
         return float(np.dot(precision, steps))
 
     def summarize(self):
-        """The evaluator's dictionary (allAp, allAp50%, classes[name][ap | ap50%]) plus "resultApMatrix"."""
+        """The evaluator's dictionary (allAp, allAp50%, classes[name][ap | ap50%]) plus "resultApMatrix"; with
+        distances also allAp50m, allAp100m, allAp50%50m and per class ap50m, ap100m, ap50%50m."""
         ap = self.ap_matrix()
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", RuntimeWarning)             # no ground truth at all: nan, not a warning
-            res = {"allAp": float(np.nanmean(ap[0])), "allAp50%": float(np.nanmean(ap[0, :, 0])), "classes": {}}
+            res = {"allAp": float(np.nanmean(ap[0])), "allAp50%": float(np.nanmean(ap[0, :, 0]))}
+            if self.distances:                                          # settings 1 and 2: within 100 m, within 50 m
+                res.update({"allAp50m": float(np.nanmean(ap[2])), "allAp100m": float(np.nanmean(ap[1])),
+                            "allAp50%50m": float(np.nanmean(ap[2, :, 0]))})
+        res["classes"] = {}
         for li, name in enumerate(self.protocol.inst_labels):
             res["classes"][name] = {"ap": float(np.average(ap[0, li])), "ap50%": float(ap[0, li, 0])}
+            if self.distances:
+                res["classes"][name].update({"ap50m": float(np.average(ap[2, li])),
+                                             "ap100m": float(np.average(ap[1, li])), "ap50%50m": float(ap[2, li, 0])})
         res["resultApMatrix"] = ap
         return res
 
 
+def has_distances(res):
+    """Whether a summarize() dictionary carries the distance averages."""
+    return "allAp100m" in res
+
+
 def results_json(res, protocol=CITYSCAPES):
-    """The dictionary the evaluator writes as resultInstanceLevelSemanticLabeling.json."""
-    return {"averages": {k: v for k, v in res.items() if k != "resultApMatrix"}, "overlaps": OVERLAPS.tolist(),
-            "minRegionSizes": MIN_REGION_SIZES.tolist(), "instLabels": list(protocol.inst_labels),
-            "resultApMatrix": res["resultApMatrix"].tolist()}
+    """The dictionary the evaluator writes as resultInstanceLevelSemanticLabeling.json.  With distances it gains the
+    evaluator's distanceThresholds and minStereoDensities; JSON has no infinity, so the unbounded first setting is
+    written as null (+inf and -inf alike: "no bound")."""
+    out = {"averages": {k: v for k, v in res.items() if k != "resultApMatrix"}, "overlaps": OVERLAPS.tolist(),
+           "minRegionSizes": MIN_REGION_SIZES.tolist(), "instLabels": list(protocol.inst_labels),
+           "resultApMatrix": res["resultApMatrix"].tolist()}
+    if has_distances(res):
+        finite = lambda a: [float(v) if np.isfinite(v) else None for v in a]   # noqa: E731
+        out["distanceThresholds"] = finite(DISTANCE_THS)
+        out["minStereoDensities"] = finite(DISTANCE_CONFS)
+    return out
+
+
+DISTANCE_COLUMNS = (("AP_50m", "ap50m", "allAp50m"), ("AP_100m", "ap100m", "allAp100m"),
+                    ("AP_50%50m", "ap50%50m", "allAp50%50m"))
 
 
 def format_results(res, protocol=CITYSCAPES):
-    """The evaluator's result table as text."""
+    """The evaluator's result table as text: 50 columns wide, 90 with the three distance columns."""
+    if has_distances(res):
+        lines = ["", "#" * 90, "{:<15}".format("what") + ":" + "{:>15}".format("AP") + "{:>15}".format("AP_50%")
+                 + "".join("{:>15}".format(c[0]) for c in DISTANCE_COLUMNS), "#" * 90]
+        for name in protocol.inst_labels:
+            c = res["classes"][name]
+            lines.append("{:<15}".format(name) + ":" + "{:>15.3f}".format(c["ap"]) + "{:>15.3f}".format(c["ap50%"])
+                         + "".join("{:>15.3f}".format(c[k[1]]) for k in DISTANCE_COLUMNS))
+        lines += ["-" * 90, "{:<15}".format("average") + ":" + "{:>15.3f}".format(res["allAp"])
+                  + "{:>15.3f}".format(res["allAp50%"])
+                  + "".join("{:>15.3f}".format(res[k[2]]) for k in DISTANCE_COLUMNS), ""]
+        return "\n".join(lines)
     lines = ["", "#" * 50, "{:<15}".format("what") + ":" + "{:>15}".format("AP") + "{:>15}".format("AP_50%"), "#" * 50]
     for name in protocol.inst_labels:
         c = res["classes"][name]
@@ -342,15 +431,28 @@ def read_pred_info(txt_path):
     return out
 
 
-def evaluate_result_dir(pred_dir, gt_files, device=None, protocol=CITYSCAPES):
+def evaluate_result_dir(pred_dir, gt_files, device=None, protocol=CITYSCAPES, disparity_dir=None, camera_dir=None):
     """Scores a result directory in the protocol's layout (Cityscapes: `<image>*.txt` listing `masks/*.png`; KITTI:
     `<base name>.txt`; IDD: `<city>/<frame>*.txt`, both with the masks next to the text file), searched below pred_dir
-    by the key of each ground-truth file.  Masks are uploaded image by image."""
+    by the key of each ground-truth file.  Masks are uploaded image by image.  With disparity_dir and camera_dir
+    (Cityscapes) the three distance settings are scored: every frame needs its disparity and camera file."""
     import torch
     from PIL import Image
     dev = device or torch.device("cuda")
     txts = [os.path.join(r, f) for r, _, files in os.walk(pred_dir) for f in files if f.endswith(".txt")]
-    ev = InstanceLevelEvaluator(protocol)
+    dist_files = None
+    if disparity_dir or camera_dir:
+        from . import distances
+        if not (disparity_dir and camera_dir):
+            raise ValueError("disparity_dir and camera_dir come together")
+        if protocol is not CITYSCAPES:
+            raise ValueError("distances are scored for cityscapes only: %s" % distances.REFUSED.get(
+                {"kitti": "kitti_poly"}.get(protocol.name, protocol.name), "no disparity convention"))
+        dist_files = distances.find_files(disparity_dir, camera_dir)
+        for gt in gt_files:                                                # before anything is scored
+            base = os.path.basename(gt)
+            distances.frame_files(dist_files, protocol.gt_key("", base) or os.path.splitext(base)[0], base)
+    ev = InstanceLevelEvaluator(protocol, distances=dist_files is not None)
     for gt in gt_files:
         root, base = os.path.split(gt)
         key = protocol.gt_key(root, base)
@@ -369,5 +471,12 @@ def evaluate_result_dir(pred_dir, gt_files, device=None, protocol=CITYSCAPES):
             if m.shape != ids.shape:
                 raise ValueError("%s is %s, the ground truth %s is %s" % (path, m.shape, gt, ids.shape))
             masks[k] = m
-        ev.add_image(torch.from_numpy(masks).to(dev), [p[1] for p in info], [p[2] for p in info], ids)
+        extra = {}
+        if dist_files is not None:
+            disp_path, cam_path = distances.frame_files(dist_files, key, base)
+            disp = distances.read_disparity(disp_path)
+            if disp.shape != ids.shape:
+                raise ValueError("%s is %s, the ground truth %s is %s" % (disp_path, disp.shape, gt, ids.shape))
+            extra = {"disparity": disp, "camera": distances.read_camera(cam_path)}
+        ev.add_image(torch.from_numpy(masks).to(dev), [p[1] for p in info], [p[2] for p in info], ids, **extra)
     return ev.summarize()

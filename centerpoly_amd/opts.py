@@ -146,6 +146,14 @@ class opts(object):
         p.add_argument("--boundary_ratio", type=float, default=0.005,
                        help="--boundary: the band's width as a share of the image diagonal, d = max(1, round(ratio * "
                             "diagonal)), 11 pixels at 2048 x 1024 (0.02 is usual for COCO-sized images); d <= 64")
+        p.add_argument("--disparity_dir", default="",
+                       help="directory searched recursively for <city>_<seq>_<frame>_disparity.png (16 bit): with it "
+                            "(and --camera_dir, --gt_dir) the instance-level AP is also scored within 100 m and 50 m "
+                            "(AP_100m, AP_50m), by the median disparity of every ground-truth instance on the GPU; "
+                            "cityscapes only")
+        p.add_argument("--camera_dir", default="",
+                       help="directory searched recursively for <city>_<seq>_<frame>_camera.json (extrinsic.baseline, "
+                            "intrinsic.fx); needed with --disparity_dir")
         p.add_argument("--not_prefetch_test", action="store_true")
         p.add_argument("--test_batch_size", type=int, default=1,
                        help="test.py: images per network launch (detector.run_batch); 1 keeps the per-image loop. "
@@ -226,6 +234,18 @@ class opts(object):
                                   "truth found there")
             if not (math.isfinite(opt.boundary_ratio) and opt.boundary_ratio > 0):
                 self.parser.error("--boundary_ratio must be finite and > 0 (got %r)" % opt.boundary_ratio)
+        if opt.disparity_dir or opt.camera_dir:
+            from .datasets.evaluation import distances
+            if not (opt.disparity_dir and opt.camera_dir):
+                self.parser.error("--disparity_dir and --camera_dir come together: a disparity becomes a distance "
+                                  "through the frame's baseline and focal length")
+            if opt.dataset not in distances.DATASETS:
+                self.parser.error("--disparity_dir scores %s only; dataset %r is refused: %s"
+                                  % (", ".join(distances.DATASETS), opt.dataset,
+                                     distances.REFUSED.get(opt.dataset, "it has no instance-level AP protocol here")))
+            if not opt.gt_dir:
+                self.parser.error("--disparity_dir needs --gt_dir: the distances are those of the ground-truth "
+                                  "instances found there")
         if opt.save_panoptic and opt.dataset != "cityscapes":
             self.parser.error("--save_panoptic writes %s only; dataset %r is refused: %s"
                               % ("cityscapes", opt.dataset,

@@ -506,6 +506,21 @@ int cp_instance_overlaps(const uint8_t* masks, int32_t n, const uint16_t* gt_ids
                          int32_t* void_inter, int32_t* pred_pixels, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* cp_segment_medians: per segment of an id image the exact median pair of a 16-bit value image (the disparity of a
+ * ground-truth instance, for AP 100 m / AP 50 m; datasets/evaluation/distances.py turns it into metres).
+ *   ids      DEVICE uint16 [H][W], an id image         values  DEVICE uint16 [H][W], 0 = no measurement
+ *   seg_ids  DEVICE int32 [G], distinct (a value outside 16 bits matches no pixel)
+ *   out      DEVICE int32 [G][4] out: pixels (ids == seg_ids[j]), valid (those with values != 0), v_lo, v_hi: the
+ *            values of 0-based ascending rank (valid - 1) / 2 and valid / 2 among the valid pixels; 0, 0 when valid == 0
+ * Exact integers.  G <= 1024, H * W < 2^31 (CP_EUNSUPPORTED otherwise); any H, W; ids and values at any element
+ * alignment (16-byte aligned images take the wide loads).  G == 0 is a no-op.  workspace:
+ * cp_segment_medians_workspace_bytes (the id -> column table, the high-byte histograms with the counts, the picked
+ * buckets, the low-byte histograms; 16-byte aligned), shorter: CP_EWORKSPACE.  All checks come before any device
+ * work.  Six launches whatever G and the content, nothing is read back in between. */
+size_t cp_segment_medians_workspace_bytes(int32_t G, int32_t H, int32_t W);
+int cp_segment_medians(const uint16_t* ids, const uint16_t* values, int32_t H, int32_t W, const int32_t* seg_ids,
+                       int32_t G, int32_t* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* cp_writer_instances: the writer's selection for ONE image on the device -- image_instances plus the label, flag and
  * confidence bookkeeping of format_and_write_to_cityscapes (cityscapes.py:225-238, 266-281) -- from detection rows in
  * the layout cp_polydet_post_process writes to the instance list cp_instance_masks and the evaluator read.

@@ -13,7 +13,11 @@ resultPixelLevelSemanticLabeling.json is written to save_dir and run_test's dict
 table follows, resultPanopticSemanticLabeling.json is written and the dict gains "panoptic"; --save_panoptic writes
 the maps in COCO panoptic format under `<save_dir>/panoptic/`.  With --boundary (and --gt_dir; cityscapes, kitti_poly,
 IDD) the masks drawn for the AP also go through cp_boundary_overlaps (evaluation/boundary.py): the Boundary AP table
-follows the AP table, resultBoundaryInstanceLevel.json is written and the dict gains "boundary".  `--dataset synthetic`
+follows the AP table, resultBoundaryInstanceLevel.json is written and the dict gains "boundary".  With --disparity_dir
+and --camera_dir (and --gt_dir, cityscapes) the loader also reads every frame's 16-bit disparity image and camera file,
+the ground-truth instances' median disparities come from cp_segment_medians in the same read
+(evaluation/distances.py), the AP table gets the evaluator's AP_50m / AP_100m / AP_50%50m columns and the dict gains
+"allAp100m", "allAp50m" and "allAp50%50m".  `--dataset synthetic`
 feeds hash-generated uint8 arrays (no files)."""
 import os
 import sys
@@ -86,14 +90,19 @@ def run_test(opt, evaluate=True):
                   + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
         dataset.run_eval(results, opt.save_dir)
         return {"ap": None, "results": results, "dataset": dataset, "stamps": []}
-    evaluator = gt_files = protocol = None
+    evaluator = gt_files = protocol = dist_files = None
     if getattr(opt, "gt_dir", "") and (getattr(dataset, "scores_ap", False) or getattr(dataset, "ap_protocol", None)):
         from centerpoly_amd.datasets.evaluation import instance_level
         if not os.path.isdir(opt.gt_dir):
             raise FileNotFoundError("--gt_dir %s is not a directory" % opt.gt_dir)
         protocol = instance_level.PROTOCOLS[getattr(dataset, "ap_protocol", None) or "cityscapes"]
         gt_files = instance_level.find_gt_files(opt.gt_dir, protocol)
-        evaluator = instance_level.InstanceLevelEvaluator(protocol)
+        if getattr(opt, "disparity_dir", "") or getattr(opt, "camera_dir", ""):
+            from centerpoly_amd.datasets.evaluation import distances
+            if opt.dataset not in distances.DATASETS or not (opt.disparity_dir and opt.camera_dir):
+                raise ValueError("--disparity_dir needs --camera_dir and the cityscapes data set")
+            dist_files = distances.find_files(opt.disparity_dir, opt.camera_dir)
+        evaluator = instance_level.InstanceLevelEvaluator(protocol, distances=dist_files is not None)
     pixel = None
     save_pan, pan_entries, pan_dir = getattr(opt, "save_panoptic", False), [], os.path.join(opt.save_dir, "panoptic")
     pan = None
@@ -113,8 +122,8 @@ def run_test(opt, evaluate=True):
         from centerpoly_amd.datasets.evaluation import boundary
         if evaluator is None:
             raise ValueError("--boundary needs --gt_dir and a data set with an AP protocol (cityscapes, kitti_poly, IDD)")
-        bnd = boundary.BoundaryEvaluator(protocol, opt.boundary_ratio)
-    images = eval_images.EvalImages(dataset, gt_files, protocol)
+        bnd = boundary.BoundaryEvaluator(protocol, opt.boundary_ratio, distances=dist_files is not None)
+    images = eval_images.EvalImages(dataset, gt_files, protocol, dist_files)
     stamps = [time.time()]
     ind = -1
     for items in eval_images.group(eval_images.iterate(images, not opt.not_prefetch_test, opt.num_workers), batch_size,
@@ -123,12 +132,13 @@ def run_test(opt, evaluate=True):
             ind += 1
             results[item["img_id"]] = res
             if evaluator is not None:
-                if bnd is None:
-                    dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"],
-                                                   item["gt_table"], evaluator)
-                else:                                                      # the same masks, the band tables in the same read
-                    dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"],
-                                                   item["gt_table"], evaluator, boundary=bnd)
+                extra = {}
+                if bnd is not None:                                        # the same masks, the band tables in the same read
+                    extra["boundary"] = bnd
+                if dist_files is not None:                                 # the instances' median disparities, the same read
+                    extra["distances"] = (item["disparity"], item["camera"])
+                dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"], item["gt_table"],
+                                               evaluator, **extra)
             if save_ids or save_masks or pixel is not None or pan is not None or save_pan:
                 file_name = dataset.coco.loadImgs(ids=[item["img_id"]])[0]["file_name"]
                 maps = detector.instances(res, image=b)                    # once for the files and the score
@@ -151,6 +161,8 @@ def run_test(opt, evaluate=True):
     else:
         ap = dataset.finish_scored_eval(results, opt.save_dir, evaluator)
     out = {"ap": ap, "results": results, "dataset": dataset, "stamps": stamps}
+    if dist_files is not None and evaluate:
+        out.update({k: dataset.last_summary[k] for k in ("allAp100m", "allAp50m", "allAp50%50m")})
     if bnd is not None and evaluate:
         out["boundary"] = bnd.summarize()
         print(boundary.format_results(out["boundary"], protocol))
