@@ -118,6 +118,9 @@ _SIGNATURES = {
     "cp_panoptic_pairs_workspace_bytes": (c_size_t, []),
     "cp_panoptic_pairs": (c_int32, [_P, c_int32, _P] + [c_int32] * 5 + [_P, _P, _P, _P, c_size_t, _P]),
     "cp_panoptic_match": (c_int32, [_P, _P, c_int32, _P, c_int32, _P, _P, _P, _P, _P, _P]),
+    "cp_map_pairs": (c_int32, [_P, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P]),
+    "cp_track_associate": (c_int32, [_P, c_int32, _P, _P, _P, _P, ctypes.c_double, c_int32, c_int32, _P, _P, _P, _P]),
+    "cp_track_update": (c_int32, [_P, c_int32, _P, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, _P, _P]),
     "cp_boundary_overlaps_workspace_bytes": (c_size_t, [c_int32] * 5),
     "cp_boundary_overlaps": (c_int32, [_P, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, _P, _P,
                                        _P, c_size_t, _P]),

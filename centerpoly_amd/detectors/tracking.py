@@ -1,0 +1,254 @@
+"""Instance tracking: link the instances of consecutive frames by the IoU of the pixels they own ("instance tracking" in
+include/centerpoly_hip.h, pinned by tests/golden/tracking_host.py; not in the reference).
+
+A tracker belongs to one canvas and keeps its memory map and slot table on the device.  A step issues three calls on
+the current stream -- cp_map_pairs (memory map against the frame's owner map), cp_track_associate (greedy matching, new
+tracks, ageing, one workgroup) and cp_track_update (the new memory map and the id image) -- and one copy brings the small
+tables back.  The defaults iou_thresh = 0.3 and max_age = 0 are this project's untuned choices."""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from .. import _C
+
+SLOTS = 256                                             # CP_TRACK_SLOTS
+MAX_INSTANCES = 128
+MAX_ROWS, MAX_COLS = 1024, 255                          # cp_map_pairs
+NONE = 0xffff
+TOO_MANY = "more than 256 tracks alive"
+# the state buffer, int32: slots [256][5], next_id, status, inst [128][5], assigned (256 bytes)
+O_NEXT = SLOTS * 5
+O_STATUS = O_NEXT + 1
+O_INST = O_STATUS + 1
+O_ASSIGNED = O_INST + MAX_INSTANCES * 5
+STATE_INTS = O_ASSIGNED + SLOTS // 4
+
+
+def _host_ptr(a):
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def as_bits16(t):
+    """A device tensor of 16-bit integers as the kernels take it (int16 holding the bits)."""
+    if t.dtype == torch.int16:
+        return t
+    if t.dtype == getattr(torch, "uint16", None):
+        return t.view(torch.int16)
+    raise ValueError("a 16-bit map must be int16 or uint16, got %s" % t.dtype)
+
+
+def map_pairs(a, b, R, n, row_of=None, out=None):
+    """cp_map_pairs on device tensors: a 16-bit [H, W], b uint8 [H, W], optional row_of 16-bit [65536].  Returns the
+    device table int32 [R + 1, n + 1] (a view of `out` when given), the none row and column last."""
+    a = as_bits16(a)
+    if a.dim() != 2 or b.dim() != 2 or b.dtype != torch.uint8 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError("map_pairs takes a 16-bit map and a uint8 map of one shape [H, W], got %s %s and %s %s"
+                         % (a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+    R, n = int(R), int(n)
+    if not (0 <= R <= MAX_ROWS and 0 <= n <= MAX_COLS):
+        raise ValueError("map_pairs: R = %d rows (at most %d), n = %d columns (at most %d)" % (R, MAX_ROWS, n, MAX_COLS))
+    if row_of is not None:
+        row_of = as_bits16(row_of)
+        if row_of.numel() != 65536:
+            raise ValueError("row_of must hold 65536 entries, got %d" % row_of.numel())
+    H, W = (int(v) for v in a.shape)
+    cells = (R + 1) * (n + 1)
+    if out is None:
+        out = torch.empty((cells,), dtype=torch.int32, device=a.device)
+    _C.check(_C.lib().cp_map_pairs(_C.ptr(a), _C.ptr(row_of), R, _C.ptr(b), n, H, W, _C.ptr(out), _C.stream()),
+             "cp_map_pairs")
+    return out[:cells].view(R + 1, n + 1)
+
+
+def _check_params(iou_thresh, max_age):
+    if not (math.isfinite(iou_thresh) and 0 < iou_thresh <= 1):
+        raise ValueError("iou_thresh must be finite and in (0, 1], got %r" % (iou_thresh,))
+    if int(max_age) != max_age or max_age < 0:
+        raise ValueError("max_age must be an integer >= 0, got %r" % (max_age,))
+
+
+def _associate(state, pairs, n, label, live, iou_thresh, max_age, t):
+    at = lambda o: ctypes.c_void_p(state.data_ptr() + 4 * o)              # noqa: E731
+    _C.check(_C.lib().cp_track_associate(_C.ptr(pairs), n, _host_ptr(label) if n else None,
+                                         _host_ptr(live) if n else None, at(0), at(O_NEXT), float(iou_thresh),
+                                         int(max_age), int(t), at(O_INST), at(O_ASSIGNED), at(O_STATUS), _C.stream()),
+             "cp_track_associate")
+
+
+def _instances(n, label, live):
+    n = int(n)
+    if not 0 <= n <= MAX_INSTANCES:
+        raise ValueError("%d instances in one frame, more than %d" % (n, MAX_INSTANCES))
+    label = np.ascontiguousarray(np.asarray(label).reshape(-1)[:n], np.int32)
+    live = np.ascontiguousarray(np.asarray(live).reshape(-1)[:n] != 0, np.uint8)
+    if len(label) < n or len(live) < n:
+        raise ValueError("%d labels and %d live flags for %d instances" % (len(label), len(live), n))
+    return n, label, live
+
+
+def _split_state(host, n):
+    return {"slots": host[:O_NEXT].reshape(SLOTS, 5).copy(), "next_id": int(host[O_NEXT]), "status": int(host[O_STATUS]),
+            "inst": host[O_INST:O_INST + 5 * n].reshape(n, 5).copy(),
+            "assigned": host[O_ASSIGNED:O_ASSIGNED + SLOTS // 4].view(np.uint8).copy()}
+
+
+def associate(pairs, n, label, live, slots, next_id, iou_thresh=0.3, max_age=0, t=0):
+    """cp_track_associate on a device pair table int32 [257, n + 1] and a host slot table int [256, 5]: the dictionary
+    {slots, next_id, inst [n, 5], assigned [256], status} after the step, as host arrays.  With status 1 (more than 256
+    tracks alive) slots and next_id are the ones given and inst / assigned are not meaningful."""
+    _check_params(iou_thresh, max_age)
+    n, label, live = _instances(n, label, live)
+    if pairs.dtype != torch.int32 or pairs.numel() != (SLOTS + 1) * (n + 1):
+        raise ValueError("the pair table must be int32 [%d, %d], got %s %s" % (SLOTS + 1, n + 1, pairs.dtype,
+                                                                             tuple(pairs.shape)))
+    host = np.zeros((STATE_INTS,), np.int32)
+    host[:O_NEXT] = np.asarray(slots, np.int32).reshape(-1)
+    host[O_NEXT] = int(next_id)
+    state = torch.from_numpy(host).to(pairs.device)
+    _associate(state, pairs.contiguous(), n, label, live, iou_thresh, max_age, t)
+    return _split_state(state.cpu().numpy(), n)
+
+
+class TrackedFrame(object):
+    """What InstanceTracker.step returns.
+      ids                device int32 [H, W]: label * multiplier + track_id of the pixel's owner, 0 where none
+      track_of_instance  device int32 [n]: the track id of every instance, 0 for a dead one
+      table              host dict, read back in one copy: n, track_id / slot / is_new / inter / union (arrays over the
+                         n instances; slot -1 for a dead instance, inter = union = 0 for a new track), alive (int
+                         [A, 6] rows slot, track_id, label, first_frame, last_seen, hits of the occupied slots), slots
+                         (the whole table [256, 5]), assigned ([256], slots that took an instance in this frame),
+                         next_id, status
+      frame              the frame counter t of this step; multiplier"""
+
+    def __init__(self, ids, track_of_instance, table, frame, multiplier):
+        self.ids, self.track_of_instance, self.table, self.frame, self.multiplier = ids, track_of_instance, table, frame, multiplier
+
+
+class InstanceTracker(object):
+    """InstanceTracker(canvas = (width, height)).step(maps) for the InstanceMaps of consecutive frames."""
+
+    def __init__(self, canvas, iou_thresh=0.3, max_age=0, multiplier=None, device=None):
+        W, H = (int(v) for v in canvas)
+        if W < 1 or H < 1:
+            raise ValueError("the canvas must be at least 1 x 1 (width, height), got %r" % (canvas,))
+        _check_params(iou_thresh, max_age)
+        if multiplier is not None and int(multiplier) < 1:
+            raise ValueError("multiplier must be >= 1, got %r" % (multiplier,))
+        self.canvas, self.iou_thresh, self.max_age = (W, H), float(iou_thresh), int(max_age)
+        self.multiplier = None if multiplier is None else int(multiplier)
+        self.device = torch.device(device if device is not None else "cuda")
+        if self.device.type != "cuda":
+            raise _C.NativeError("InstanceTracker needs a HIP device (got %s); there is no CPU fallback" % self.device)
+        _C.lib()
+        self.pairs = torch.empty(((SLOTS + 1) * (MAX_INSTANCES + 1),), dtype=torch.int32, device=self.device)
+        self.reset()
+
+    def reset(self):
+        """Forget every track: the state of a new tracker."""
+        W, H = self.canvas
+        self.mem = torch.full((H, W), -1, dtype=torch.int16, device=self.device)       # 0xffff
+        host = np.zeros((STATE_INTS,), np.int32)
+        host[O_NEXT] = 1
+        self.state = torch.from_numpy(host).to(self.device)
+        self.frame = 0
+
+    def step(self, maps):
+        """One frame from its InstanceMaps (detector.instances / instance_maps)."""
+        if tuple(maps.canvas) != self.canvas:
+            raise ValueError("the tracker's canvas is %d x %d and the frame's is %d x %d: call reset() on a tracker of "
+                             "the new canvas, tracks do not carry over" % (self.canvas + tuple(maps.canvas)))
+        t = maps.table
+        return self.step_index(maps.index, t["n"], t["label"], t["live"],
+                               maps.multiplier if self.multiplier is None else self.multiplier)
+
+    def enqueue(self, index, n, label, live, multiplier):
+        """The three calls of a step for frame `self.frame`, nothing read back and the frame counter left alone: the id
+        image.  Arguments as _instances returns them; step_index is the checked way in."""
+        W, H = self.canvas
+        pairs = map_pairs(self.mem, index, SLOTS, n, out=self.pairs)
+        _associate(self.state, pairs, n, label, live, self.iou_thresh, self.max_age, self.frame)
+        ids = torch.empty((H, W), dtype=torch.int32, device=self.device)
+        at = lambda o: ctypes.c_void_p(self.state.data_ptr() + 4 * o)     # noqa: E731
+        _C.check(_C.lib().cp_track_update(_C.ptr(index), n, _host_ptr(label) if n else None, H, W, at(0), at(O_INST),
+                                          at(O_ASSIGNED), at(O_STATUS), multiplier, _C.ptr(self.mem), _C.ptr(ids),
+                                          _C.stream()), "cp_track_update")
+        return ids
+
+    def step_index(self, index, n, label, live, multiplier=None):
+        """One frame from its owner map: index device uint8 [H, W] (255 = none), n instances, their labels and live
+        flags (host)."""
+        W, H = self.canvas
+        if multiplier is None:
+            multiplier = self.multiplier
+        if multiplier is None or int(multiplier) < 1:
+            raise ValueError("step_index needs a multiplier >= 1 (the tracker was made without one)")
+        if index.dtype != torch.uint8 or tuple(index.shape) != (H, W):
+            raise ValueError("the owner map must be uint8 [%d, %d], got %s %s: a canvas change needs a new tracker"
+                             % (H, W, index.dtype, tuple(index.shape)))
+        if index.device != self.mem.device:
+            raise ValueError("the owner map is on %s, the tracker on %s" % (index.device, self.mem.device))
+        n, label, live = _instances(n, label, live)
+        ids = self.enqueue(index.contiguous(), n, label, live, int(multiplier))
+        track_of_instance = self.state[O_INST:O_INST + 5 * n].view(n, 5)[:, 1].clone()
+        tab = _split_state(self.state.cpu().numpy(), n)                   # the one copy
+        if tab["status"]:
+            raise ValueError("%s in frame %d: the step changed nothing; lower --track_max_age or raise --thresh"
+                             % (TOO_MANY, self.frame))
+        inst, slots = tab.pop("inst"), tab["slots"]
+        occupied = np.flatnonzero(slots[:, 0])
+        tab.update({"n": n, "slot": inst[:, 0], "track_id": inst[:, 1], "inter": inst[:, 2], "union": inst[:, 3],
+                    "is_new": inst[:, 4] != 0, "alive": np.concatenate([occupied[:, None], slots[occupied]], 1)})
+        frame = self.frame
+        self.frame += 1
+        return TrackedFrame(ids, track_of_instance, tab, frame, int(multiplier))
+
+
+def save_tracks(maps, tracked, out_dir, stem):
+    """--track --save_ids: `<stem>_tracks.json` (per live instance: track id, label, score, box, is_new) and
+    `<stem>_trackIds.png` (16 bit, label * multiplier + track_id) in out_dir.  The PNG cannot hold a track id that
+    reaches the multiplier: a ValueError that names the frame; the JSON has no such limit and is written first.
+    Returns the two paths."""
+    import json
+    import os
+
+    from ..datasets.ground_truth import write_id_png
+    os.makedirs(out_dir, exist_ok=True)
+    paths = [os.path.join(out_dir, stem + "_tracks.json"), os.path.join(out_dir, stem + "_trackIds.png")]
+    t, k_tab = maps.table, tracked.table
+    entries = [{"track_id": int(k_tab["track_id"][k]), "label_id": int(t["label"][k]),
+                "class_name": maps.names.get(int(t["label"][k]), ""), "score": float(t["score"][k]),
+                "box": [int(v) for v in t["box"][k]], "is_new": bool(k_tab["is_new"][k])}
+               for k in range(int(t["n"])) if t["live"][k]]
+    with open(paths[0], "w") as f:
+        json.dump({"frame": int(tracked.frame), "width": maps.canvas[0], "height": maps.canvas[1],
+                   "multiplier": int(tracked.multiplier), "instances": entries}, f)
+    worst = max([e["track_id"] for e in entries], default=0)
+    if worst >= tracked.multiplier or max([e["label_id"] for e in entries], default=0) * tracked.multiplier + worst > 65535:
+        raise ValueError("%s (frame %d of its sequence): track id %d does not fit label * %d + track_id in 16 bits; "
+                         "%s holds the tracks" % (stem, tracked.frame, worst, tracked.multiplier, paths[0]))
+    write_id_png(paths[1], tracked.ids, 16)
+    return paths
+
+
+class SequenceTracker(object):
+    """The drivers' tracker: frames arrive in order with their file names, the tracker starts anew where the sequence
+    key (evaluation.tracking.sequence_key) changes, on a tracker of the frame's canvas."""
+
+    def __init__(self, iou_thresh=0.3, max_age=0):
+        self.iou_thresh, self.max_age = iou_thresh, max_age
+        self.tracker, self.key = None, None
+
+    def step(self, file_name, maps):
+        """(sequence key, TrackedFrame) of the frame."""
+        from ..datasets.evaluation.tracking import sequence_key
+        key = sequence_key(file_name)
+        if key != self.key:
+            if self.tracker is None or self.tracker.canvas != tuple(maps.canvas) or \
+                    self.tracker.device != maps.index.device:
+                self.tracker = InstanceTracker(maps.canvas, self.iou_thresh, self.max_age, device=maps.index.device)
+            else:
+                self.tracker.reset()
+            self.key = key
+        return key, self.tracker.step(maps)

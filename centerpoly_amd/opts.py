@@ -154,6 +154,21 @@ class opts(object):
         p.add_argument("--camera_dir", default="",
                        help="directory searched recursively for <city>_<seq>_<frame>_camera.json (extrinsic.baseline, "
                             "intrinsic.fx); needed with --disparity_dir")
+        p.add_argument("--track", action="store_true",
+                       help="demo.py / test.py: link the instances (detector.instances) of consecutive frames by the IoU "
+                            "of the pixels they own, on the GPU; the frames run in sorted / loader order and one "
+                            "sequence is one directory (plus <city>_<seq> of <city>_<seq>_<frame> names).  With "
+                            "--save_ids also <stem>_trackIds.png (16 bit, label * multiplier + track id) and "
+                            "<stem>_tracks.json; test.py with --gt_dir scores MOTSA / sMOTSA / MOTSP (the ground-truth "
+                            "ids must be consistent over a sequence); not for the synthetic set, not with --debug 3")
+        p.add_argument("--track_iou", type=float, default=0.3,
+                       help="--track: least mask IoU between a track's remembered pixels and an instance of its label, "
+                            "finite and in (0, 1]; 0.3 is this project's untuned choice")
+        p.add_argument("--track_max_age", type=int, default=0,
+                       help="--track: frames a track may go unseen before it ends, >= 0; 0 (a track not seen in a frame "
+                            "ends there) is this project's untuned choice")
+        p.add_argument("--track_ignore_id", type=int, default=10000,
+                       help="--track with --gt_dir: the ground-truth id of the ignore region (10000 in KITTI MOTS)")
         p.add_argument("--not_prefetch_test", action="store_true")
         p.add_argument("--test_batch_size", type=int, default=1,
                        help="test.py: images per network launch (detector.run_batch); 1 keeps the per-image loop. "
@@ -253,6 +268,17 @@ class opts(object):
                                  if opt.dataset == "synthetic" else
                                  "cityscapes_panoptic_<split>.json is the Cityscapes format and carries Cityscapes label "
                                  "ids, which this data set's instances do not have"))
+        if not (opt.track_iou == opt.track_iou and 0 < opt.track_iou <= 1):
+            self.parser.error("--track_iou must be finite and in (0, 1] (got %r)" % opt.track_iou)
+        if opt.track_max_age < 0:
+            self.parser.error("--track_max_age must be at least 0 (got %d)" % opt.track_max_age)
+        if opt.track:
+            if opt.dataset == "synthetic":
+                self.parser.error("--track links the instance maps a data set's result writer draws; dataset "
+                                  "'synthetic' is refused: the synthetic set has no result writer and no sequences")
+            if opt.debug == 3:
+                self.parser.error("--track cannot be combined with --debug 3: the matplotlib display is not built, the "
+                                  "detector would refuse the first frame of the sequence")
         if opt.test_batch_size < 1:
             self.parser.error("--test_batch_size must be at least 1 (got %d)" % opt.test_batch_size)
         if opt.test_batch_size > 1 and opt.debug > 0:

@@ -7,6 +7,8 @@ the reference prints it, with the time of the pictures appended.  `--load_model 
 --save_ids / --save_masks also write every image's instance maps (detector.instances, drawn by the writer of --dataset
 on the image's own canvas from the detections above --thresh) under `<save_dir>/instances/`: `<stem>_instanceIds.png`,
 `<stem>_labelIds.png` and `<stem>.json`; `<stem>.txt` and `masks/<stem>_<k>.png`.
+--track takes the sorted frames of the directory as one sequence and links their instances (detectors/tracking.py);
+with --save_ids it also writes `<stem>_trackIds.png` and `<stem>_tracks.json` there.
 There is no video decoder here: `webcam` and video files are refused."""
 import os
 import sys
@@ -47,14 +49,22 @@ def demo(opt):
     detector = detector_factory[opt.task](opt)
     out = []
     pan_entries = []
+    seq = None
+    if getattr(opt, "track", False):
+        from centerpoly_amd.detectors import tracking
+        seq = tracking.SequenceTracker(opt.track_iou, opt.track_max_age)
     for name in names:
         ret = detector.run(name)
         print("".join("{} {:.3f}s |".format(stat, ret[stat]) for stat in time_stats)
               + "vis {:.3f}s |".format(ret["vis_time"]))
-        if opt.save_ids or opt.save_masks:
+        if opt.save_ids or opt.save_masks or seq is not None:
             from centerpoly_amd.detectors import instances
             maps = detector.instances(ret["results"])
             inst_dir, stem = os.path.join(opt.save_dir, "instances"), instances.image_stem(name)
+            if seq is not None:                                  # the directory is one sequence
+                ret["tracked"] = seq.step(os.path.join(os.path.dirname(name), "frame"), maps)[1]
+                if opt.save_ids:
+                    tracking.save_tracks(maps, ret["tracked"], inst_dir, stem)
             if opt.save_ids:
                 instances.save_ids(maps, inst_dir, stem)
             if opt.save_masks:

@@ -57,7 +57,7 @@ extern "C" {
                               cp_conv1x1_stream_*, cp_conv3x3_stream_*, cp_instance_map(_workspace_bytes),
                               cp_pixel_confusion(_workspace_bytes), cp_panoptic_pairs(_workspace_bytes), cp_panoptic_match,
                               cp_boundary_overlaps(_workspace_bytes), cp_polygon_overlaps(_workspace_bytes),
-                              cp_merge_detections_mask(_workspace_bytes) */
+                              cp_merge_detections_mask(_workspace_bytes), cp_map_pairs, cp_track_associate, cp_track_update */
 
 enum {
   CP_OK = 0,
@@ -703,6 +703,69 @@ int cp_panoptic_pairs(const uint8_t* index, int32_t n, const uint16_t* gt_ids, i
                       void* workspace, size_t workspace_bytes, void* stream);
 int cp_panoptic_match(const int32_t* seg, const int32_t* pairs, int32_t n, const int32_t* pred_label, int32_t L,
                       const uint8_t* label_flags, int64_t* stat, double* iou, int32_t* bad, int32_t* match, void* stream);
+
+/* ------------------------------------------------ instance tracking (detectors/tracking.py) --
+ * Links the instances of one frame (cp_instance_map's `index`) to the tracks of the frames before it by the IoU of the
+ * pixels they own.  Not in the reference tree: a capability of this library, defined here and pinned by the host
+ * statement tests/golden/tracking_host.py.
+ *
+ * A tracker belongs to one canvas (W, H) and keeps on the device
+ *   mem     uint16 [H][W]: the track slot that last owned the pixel, 0xffff for none
+ *   slots   int32 [CP_TRACK_SLOTS][5] = {track_id, label, first_frame, last_seen, hits}; track_id >= 1, 0 marks a free
+ *           slot (the whole row is then 0)
+ *   next_id int32 [1], starting at 1: track ids rise by one per new track and are never reused within a run; freed slots
+ *           are reused, lowest index first
+ * and the host keeps the frame counter t, starting at 0.  One step takes a frame's index (uint8 [H][W], 255 = none),
+ * n <= 128 instances, a label and a live flag per instance:
+ *   1. counts.  inter[s][k] = pixels with mem == s and index == k, area_mem[s] = pixels with mem == s, area_cur[k] =
+ *      pixels with index == k.  Exact integers (cp_map_pairs with R = CP_TRACK_SLOTS and no lookup).
+ *   2. association (cp_track_associate).  (s, k) is a candidate when slot s is occupied, k is live, the labels are
+ *      equal, inter > 0 and (double)inter / (double)(area_mem[s] + area_cur[k] - inter) >= iou_thresh -- one correctly
+ *      rounded float64 division of two integers against the float64 threshold.  Greedy: take the candidate of largest
+ *      IoU, compared exactly as fractions (inter_a * union_b against inter_b * union_a in 64-bit integers), ties to
+ *      the smaller track_id, then the smaller k; match it, drop its row and column, repeat until none is left.  A
+ *      matched instance takes the slot's track id, last_seen = t, hits += 1.  Every unmatched live instance, in
+ *      ascending k, takes the lowest free slot: {next_id++, label, t, t, 1}.  Then every slot with
+ *      last_seen < t - max_age is freed (max_age 0: a track not seen in this frame ends here).  If an instance finds no
+ *      free slot, status = 1 and nothing else is written: slots, next_id and (through cp_track_update) mem stay as
+ *      they were.
+ *   3. update (cp_track_update), one pass: mem[p] = the slot of the instance that owns p; else its old slot if that
+ *      slot is still occupied and took no instance in this frame (a lost track keeps what is left of its last mask, a
+ *      track seen in this frame remembers exactly its current mask); else 0xffff.  ids[p] = label * multiplier +
+ *      track_id of the owner, 0 where there is none.
+ * and then t += 1.
+ *
+ * cp_map_pairs: the pixel count of every (row, column) pair of a 16-bit map and a byte map.
+ *   a       DEVICE uint16 [H][W]                              b  DEVICE uint8 [H][W]
+ *   row_of  DEVICE uint16 [65536] or NULL (identity): the row of a value of a; a row >= R (0xffff) is "none", row R
+ *   R       rows, 0 .. 1024      n  columns, 0 .. 255: the column of a pixel is b when that is < n, else n ("none")
+ *   pairs   DEVICE int32 [R + 1][n + 1] out, zeroed by the call: row sums and column sums are the areas
+ * R > 1024, n > 255, H * W >= 2^31: CP_EUNSUPPORTED; null a, b or pairs, non-positive H or W, negative R or n, a
+ * misaligned table: CP_EINVAL.  No workspace.  Any H, any W, any alignment of a and b (a 16-byte aligned image takes
+ * 16-byte loads for its full pieces of 16 pixels, each image by itself).  Two launches; a workgroup's table lives in
+ * LDS when (R + 1) * (n + 1) <= 33153 cells (257 x 129, the tracker's whole range) and the counts go to the global
+ * table directly otherwise.  Integer atomics only: the same bits on every run.
+ *
+ * cp_track_associate: stage 2 on the pair table [CP_TRACK_SLOTS + 1][n + 1], one launch of one workgroup.
+ *   label    HOST int32 [n]      live  HOST uint8 [n], non-zero = live      slots, next_id  DEVICE, in and out
+ *   inst     DEVICE int32 [n][5] out = {slot, track_id, matched inter, matched union, is_new}; {-1, 0, 0, 0, 0} for a
+ *            dead instance, inter = union = 0 for a new track
+ *   assigned DEVICE uint8 [CP_TRACK_SLOTS] out: 1 where the slot took an instance in this frame, matched or new
+ *   status   DEVICE int32 [1] out: 0, or 1 = more than CP_TRACK_SLOTS tracks alive (nothing else was written)
+ * n > 128: CP_EUNSUPPORTED; iou_thresh outside (0, 1] or NaN, max_age < 0, t < 0, null or misaligned tables: CP_EINVAL.
+ *
+ * cp_track_update: stage 3 from the tables cp_track_associate wrote; writes nothing when status[0] != 0.
+ *   mem  DEVICE uint16 [H][W] in and out      ids  DEVICE int32 [H][W] out      label  HOST int32 [n]
+ * Limits and codes as above, multiplier >= 1; any H, W and alignment of index, mem and ids. */
+#define CP_TRACK_SLOTS 256
+int cp_map_pairs(const uint16_t* a, const uint16_t* row_of, int32_t R, const uint8_t* b, int32_t n, int32_t H, int32_t W,
+                 int32_t* pairs, void* stream);
+int cp_track_associate(const int32_t* pairs, int32_t n, const int32_t* label, const uint8_t* live, int32_t* slots,
+                       int32_t* next_id, double iou_thresh, int32_t max_age, int32_t t, int32_t* inst, uint8_t* assigned,
+                       int32_t* status, void* stream);
+int cp_track_update(const uint8_t* index, int32_t n, const int32_t* label, int32_t H, int32_t W, const int32_t* slots,
+                    const int32_t* inst, const uint8_t* assigned, const int32_t* status, int32_t multiplier,
+                    uint16_t* mem, int32_t* ids, void* stream);
 
 /* ------------------------------------------------ boundary evaluation (evaluation/boundary.py) --
  * cp_boundary_overlaps: the pixel counting of Boundary IoU / Boundary AP (Cheng et al., CVPR 2021) for ONE image --

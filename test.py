@@ -17,7 +17,12 @@ follows the AP table, resultBoundaryInstanceLevel.json is written and the dict g
 and --camera_dir (and --gt_dir, cityscapes) the loader also reads every frame's 16-bit disparity image and camera file,
 the ground-truth instances' median disparities come from cp_segment_medians in the same read
 (evaluation/distances.py), the AP table gets the evaluator's AP_50m / AP_100m / AP_50%50m columns and the dict gains
-"allAp100m", "allAp50m" and "allAp50%50m".  `--dataset synthetic`
+"allAp100m", "allAp50m" and "allAp50%50m".  With --track the instance maps of the images, in the loader's order, go
+through an instance tracker (detectors/tracking.py) that starts anew where the sequence changes (the image's directory
+plus `<city>_<seq>` of `<city>_<seq>_<frame>` names); --save_ids then also writes `<stem>_trackIds.png` and
+`<stem>_tracks.json`, and with --gt_dir -- whose instance ids must then be consistent over a sequence -- the MOTS
+measures (evaluation/tracking.py) are printed after the other tables, resultTracking.json is written and the dict gains
+"tracking".  `--dataset synthetic`
 feeds hash-generated uint8 arrays (no files)."""
 import os
 import sys
@@ -67,6 +72,10 @@ def run_test(opt, evaluate=True):
 
     save_ids, save_masks = getattr(opt, "save_ids", False), getattr(opt, "save_masks", False)
     inst_dir = os.path.join(opt.save_dir, "instances")
+
+    def instances_stem(file_name):
+        from centerpoly_amd.detectors import instances
+        return instances.image_stem(file_name)
 
     def save_instances(file_name, maps):
         """--save_ids / --save_masks: the instance maps of one image, on its own canvas."""
@@ -123,6 +132,13 @@ def run_test(opt, evaluate=True):
         if evaluator is None:
             raise ValueError("--boundary needs --gt_dir and a data set with an AP protocol (cityscapes, kitti_poly, IDD)")
         bnd = boundary.BoundaryEvaluator(protocol, opt.boundary_ratio, distances=dist_files is not None)
+    seq = mots = None
+    if getattr(opt, "track", False):
+        from centerpoly_amd.detectors import tracking
+        seq = tracking.SequenceTracker(opt.track_iou, opt.track_max_age)
+        if evaluator is not None:
+            from centerpoly_amd.datasets.evaluation import tracking as mots_eval
+            mots = mots_eval.TrackingEvaluator(protocol, opt.track_ignore_id)
     images = eval_images.EvalImages(dataset, gt_files, protocol, dist_files)
     stamps = [time.time()]
     ind = -1
@@ -139,11 +155,17 @@ def run_test(opt, evaluate=True):
                     extra["distances"] = (item["disparity"], item["camera"])
                 dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"], item["gt_table"],
                                                evaluator, **extra)
-            if save_ids or save_masks or pixel is not None or pan is not None or save_pan:
+            if save_ids or save_masks or pixel is not None or pan is not None or save_pan or seq is not None:
                 file_name = dataset.coco.loadImgs(ids=[item["img_id"]])[0]["file_name"]
                 maps = detector.instances(res, image=b)                    # once for the files and the score
                 if save_ids or save_masks:
                     save_instances(file_name, maps)
+                if seq is not None:                                        # step per image, in the loader's order
+                    key, tracked = seq.step(file_name, maps)
+                    if save_ids:
+                        tracking.save_tracks(maps, tracked, inst_dir, instances_stem(file_name))
+                    if mots is not None:
+                        mots.add_maps(key, maps, tracked, item["gt_ids"], file_name)
                 if pixel is not None:
                     pixel.add_maps(maps, item["gt_ids"], file_name)
                 if pan is not None:
@@ -178,6 +200,10 @@ def run_test(opt, evaluate=True):
         out["panoptic"] = pan.results()
         pan.print_table(out["panoptic"])
         pan.write_json(opt.save_dir, out["panoptic"])
+    if mots is not None and evaluate:
+        out["tracking"] = mots.results()
+        mots.print_table(out["tracking"])
+        mots.write_json(opt.save_dir, out["tracking"])
     return out
 
 
