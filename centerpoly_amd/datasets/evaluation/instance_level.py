@@ -480,3 +480,66 @@ def evaluate_result_dir(pred_dir, gt_files, device=None, protocol=CITYSCAPES, di
             extra = {"disparity": disp, "camera": distances.read_camera(cam_path)}
         ev.add_image(torch.from_numpy(masks).to(dev), [p[1] for p in info], [p[2] for p in info], ids, **extra)
     return ev.summarize()
+
+
+def evaluate_coco_results(results_json, annot_json, gt_files, device=None, protocol=CITYSCAPES):
+    """Scores a COCO segm results file -- a list of {"image_id", "category_id", "score", "segmentation": {"size": [H, W],
+    "counts": RLE string or list}}, made here by --save_rle or anywhere else -- with the instance-level AP.  annot_json
+    (COCO annotations) gives image_id -> file_name, matched to the ground truth by the protocol's image key, and
+    category_id -> name -> the protocol's label id (a category the protocol has no instances of is left out, as
+    evaluate_result_dir never opens such masks).  gt_files: find_gt_files' dictionary or a list of paths; every
+    ground-truth image is scored, with no prediction when the results name none.  The masks are decoded on the device
+    (utils/rle.py); a segmentation whose size is not the ground truth's, or whose counts do not fill it, is a
+    ValueError naming the entry."""
+    import json
+
+    import torch
+
+    from ...utils import rle
+    dev = device or torch.device("cuda")
+    with open(annot_json) as f:
+        annot = json.load(f)
+    with open(results_json) as f:
+        results = json.load(f)
+    name_of = {int(c["id"]): c["name"] for c in annot.get("categories", [])}
+    label_of_name = dict(zip(protocol.inst_labels, protocol.label_ids))
+    key_of = {int(im["id"]): protocol.image_key(im["file_name"]) for im in annot.get("images", [])}
+    per_key = {}
+    for i, r in enumerate(results):
+        what = "%s entry %d" % (results_json, i)
+        try:
+            img, cat, score, seg = int(r["image_id"]), int(r["category_id"]), float(r["score"]), r["segmentation"]
+        except (KeyError, TypeError, ValueError):
+            raise ValueError("%s: needs image_id, category_id, score and segmentation" % what)
+        if img not in key_of:
+            raise ValueError("%s: image_id %d is not in %s" % (what, img, annot_json))
+        if cat not in name_of:
+            raise ValueError("%s: category_id %d is not in %s" % (what, cat, annot_json))
+        if name_of[cat] in label_of_name:
+            per_key.setdefault(key_of[img], []).append((what, label_of_name[name_of[cat]], score, seg))
+    if isinstance(gt_files, dict):
+        keyed = sorted(gt_files.items())
+    else:
+        keyed = []
+        for gt in gt_files:
+            root, base = os.path.split(gt)
+            key = protocol.gt_key(root, base)
+            keyed.append((os.path.splitext(base)[0] if key is None else key, gt))
+    ev = InstanceLevelEvaluator(protocol)
+    for key, gt in keyed:
+        ids = read_gt_ids(gt)
+        mine = per_key.get(key, [])
+        for what, _, _, seg in mine:
+            size = seg.get("size") if isinstance(seg, dict) else None
+            if size is None or tuple(int(v) for v in size) != tuple(ids.shape):
+                raise ValueError("%s: the segmentation's size is %r, the ground truth %s is %s"
+                                 % (what, size, gt, list(ids.shape)))
+        if mine:
+            masks, status = rle.decode([p[3] for p in mine], dev, names=[p[0] for p in mine])
+            if status.any():
+                raise ValueError("%s: the counts do not add up to the image's %d x %d pixels"
+                                 % (mine[int(np.flatnonzero(status)[0])][0], ids.shape[0], ids.shape[1]))
+        else:
+            masks = torch.zeros((0,) + tuple(ids.shape), dtype=torch.uint8, device=dev)
+        ev.add_image(masks, [p[1] for p in mine], [p[2] for p in mine], ids)
+    return ev.summarize()

@@ -12,7 +12,8 @@ depth-resolved merge (cp_instance_map); one copy brings the small tables back.
       (class, then depth), so the priority is the depth of the instance's source row: the nearer instance wins across
       classes too, ties go to the earlier slot.  Ids are label * 256 + k (KITTI) or label * 1000 + k (IDD), the
       multiplier of the data set's evaluation protocol.
-`save_ids` and `save_masks` write what demo.py and test.py offer as --save_ids and --save_masks."""
+`save_ids`, `save_masks` and `save_rle` write what demo.py and test.py offer as --save_ids, --save_masks and --save_rle
+(the masks as COCO run-length strings, encoded on the device by utils/rle.py)."""
 import ctypes
 import json
 import os
@@ -206,6 +207,15 @@ def image_stem(name):
     return os.path.splitext(os.path.basename(str(name)))[0]
 
 
+def instance_entry(maps, k):
+    """What <stem>.json says about slot k."""
+    t = maps.table
+    return {"label_id": int(t["label"][k]), "class_name": maps.names.get(int(t["label"][k]), ""),
+            "score": float(t["score"][k]), "confidence": float(t["conf"][k]), "value": int(t["value"][k]),
+            "visible": int(t["visible"][k]), "box": [int(v) for v in t["box"][k]], "source_row": int(t["src"][k]),
+            "polygon": [[int(x), int(y)] for x, y in t["poly"][k]]}
+
+
 def save_ids(maps, out_dir, stem):
     """--save_ids: <stem>_instanceIds.png (16 bit), <stem>_labelIds.png (8 bit) and <stem>.json (one entry per live
     instance) in out_dir.  Returns the three paths."""
@@ -216,11 +226,7 @@ def save_ids(maps, out_dir, stem):
     write_id_png(paths[0], maps.ids, 16)
     write_id_png(paths[1], maps.labels, 8)
     t = maps.table
-    entries = [{"label_id": int(t["label"][k]), "class_name": maps.names.get(int(t["label"][k]), ""),
-                "score": float(t["score"][k]), "confidence": float(t["conf"][k]), "value": int(t["value"][k]),
-                "visible": int(t["visible"][k]), "box": [int(v) for v in t["box"][k]], "source_row": int(t["src"][k]),
-                "polygon": [[int(x), int(y)] for x, y in t["poly"][k]]}
-               for k in range(t["n"]) if t["live"][k]]
+    entries = [instance_entry(maps, k) for k in range(t["n"]) if t["live"][k]]
     with open(paths[2], "w") as f:
         json.dump({"width": maps.canvas[0], "height": maps.canvas[1], "multiplier": int(maps.multiplier),
                    "instances": entries}, f)
@@ -242,3 +248,47 @@ def save_masks(maps, out_dir, stem):
             f.write("%s %d %s\n" % (name, int(maps.table["label"][k]), maps.conf_text(k)))
             Image.fromarray(masks[k]).save(os.path.join(out_dir, name))
     return path
+
+
+def vertex_bounds_host(poly, margin, canvas):
+    """vertex_bounds on the host: integer vertices numpy [n, N, 2] -> int32 [n, 4]."""
+    W, H = canvas
+    p = np.asarray(poly, dtype=np.int64).reshape(len(poly), -1, 2)
+    if len(p) == 0:
+        return np.zeros((0, 4), np.int32)
+    lo, hi = p.min(1) - margin, p.max(1) + margin
+    b = np.stack([lo[:, 0].clip(0, W), lo[:, 1].clip(0, H), hi[:, 0].clip(-1, W - 1), hi[:, 1].clip(-1, H - 1)], 1)
+    far = np.abs(p).max((1, 2)) > EXACT_VERTEX
+    b[far] = [0, 0, W - 1, H - 1]
+    return np.ascontiguousarray(b, dtype=np.int32)
+
+
+def rle_instances(maps):
+    """The live instances in `maps.written()` order as (slot, entry): the entry of <stem>.json plus "bbox" ([x, y, w,
+    h] of the mask) and "segmentation" (the COCO RLE of the writer's mask `maps.masks[k]`), encoded on the device
+    within the polygons' bounds (cp_rle_encode) and read back in one copy."""
+    from ..utils import rle
+    slots, n = maps.written(), int(maps.table["n"])
+    if not slots:
+        return []
+    bounds = vertex_bounds_host(maps.table["poly"], MARGIN[maps.family], maps.canvas)
+    rles = rle.encode(masks=maps.masks[:n], bounds=bounds)
+    out = []
+    for k in slots:
+        seg = {"size": rles[k]["size"], "counts": rles[k]["counts"]}
+        entry = instance_entry(maps, k)
+        entry["bbox"] = rle.to_bbox([seg])[0]
+        entry["segmentation"] = seg
+        out.append((k, entry))
+    return out
+
+
+def save_rle(maps, out_dir, stem):
+    """--save_rle: <stem>_rle.json = {"width", "height", "instances"} in out_dir, the instances of rle_instances.
+    Returns (path, [(slot, entry)])."""
+    os.makedirs(out_dir, exist_ok=True)
+    found = rle_instances(maps)
+    path = os.path.join(out_dir, stem + "_rle.json")
+    with open(path, "w") as f:
+        json.dump({"width": maps.canvas[0], "height": maps.canvas[1], "instances": [e for _, e in found]}, f)
+    return path, found

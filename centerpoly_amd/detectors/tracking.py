@@ -7,6 +7,7 @@ tracks, ageing, one workgroup) and cp_track_update (the new memory map and the i
 tables back.  The defaults iou_thresh = 0.3 and max_age = 0 are this project's untuned choices."""
 import ctypes
 import math
+import os
 
 import numpy as np
 import torch
@@ -230,6 +231,78 @@ def save_tracks(maps, tracked, out_dir, stem):
                          "%s holds the tracks" % (stem, tracked.frame, worst, tracked.multiplier, paths[0]))
     write_id_png(paths[1], tracked.ids, 16)
     return paths
+
+
+MOTS_ID_BASE = 1000                                     # object_id = class_id * 1000 + track id (KITTI MOTS)
+
+
+def parse_class_map(text):
+    """--mots_class_map: "26:1,24:2" -> {26: 1, 24: 2} (label id : class id of the MOTS file); empty: None.  A
+    malformed pair, a negative number or a label named twice is a ValueError."""
+    if text is None or not str(text).strip():
+        return None
+    out = {}
+    for pair in str(text).split(","):
+        parts = pair.split(":")
+        try:
+            if len(parts) != 2:
+                raise ValueError
+            label, cls = int(parts[0]), int(parts[1])
+        except ValueError:
+            raise ValueError("--mots_class_map takes label:class pairs such as 26:1,24:2; %r is none" % pair)
+        if label < 0 or cls < 0 or label in out:
+            raise ValueError("--mots_class_map: label %d is negative, maps to a negative class or is named twice" % label)
+        out[label] = cls
+    return out
+
+
+def mots_lines(maps, tracked, class_map=None, what=""):
+    """The frame's lines of a MOTS text file, `frame object_id class_id H W rle`, one per live tracked instance that
+    owns a pixel: the RLE (cp_rle_encode on the owner map, so the masks of a frame are disjoint) of the pixels the
+    instance owns, class_id the label id or its image under `class_map` (a label the map lacks is skipped), object_id
+    = class_id * 1000 + track id.  A track id >= 1000 is a ValueError naming the frame."""
+    from ..utils import rle
+    t, k_tab = maps.table, tracked.table
+    n = int(t["n"])
+    keep = []
+    for k in range(n):
+        if not t["live"][k] or int(t["visible"][k]) <= 0 or int(k_tab["track_id"][k]) <= 0:
+            continue
+        label = int(t["label"][k])
+        if class_map is not None and label not in class_map:
+            continue
+        track = int(k_tab["track_id"][k])
+        if track >= MOTS_ID_BASE:
+            raise ValueError("%s (frame %d of its sequence): track id %d does not fit object_id = class_id * %d + track id"
+                             % (what, tracked.frame, track, MOTS_ID_BASE))
+        keep.append((k, label if class_map is None else class_map[label], track))
+    if not keep:
+        return []
+    rles = rle.encode(index=maps.index, n=n, bounds=np.ascontiguousarray(t["box"], np.int32).reshape(n, 4))
+    W, H = maps.canvas
+    return ["%d %d %d %d %d %s" % (tracked.frame, cls * MOTS_ID_BASE + track, cls, H, W, rles[k]["counts"])
+            for k, cls, track in keep]
+
+
+class MotsWriter(object):
+    """--track --save_rle: `<out_dir>/mots/<sequence key>.txt`, the lines of mots_lines frame after frame.  A
+    sequence's file starts anew the first time this writer sees its key."""
+
+    def __init__(self, out_dir, class_map=None):
+        self.dir, self.class_map, self.seen = os.path.join(out_dir, "mots"), class_map, set()
+
+    def path(self, key):
+        name = "_".join(p for p in str(key).replace("\\", "/").split("/") if p and p != ".") or "sequence"
+        return os.path.join(self.dir, name + ".txt")
+
+    def add(self, key, maps, tracked, what=""):
+        lines = mots_lines(maps, tracked, self.class_map, what)
+        os.makedirs(self.dir, exist_ok=True)
+        path = self.path(key)
+        with open(path, "a" if key in self.seen else "w") as f:
+            f.write("".join(line + "\n" for line in lines))
+        self.seen.add(key)
+        return path
 
 
 class SequenceTracker(object):

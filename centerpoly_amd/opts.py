@@ -127,6 +127,14 @@ class opts(object):
         p.add_argument("--save_masks", action="store_true",
                        help="demo.py / test.py: per image <stem>.txt and masks/<stem>_<k>.png under "
                             "<save_dir>/instances/, the Cityscapes result layout for every data set")
+        p.add_argument("--save_rle", action="store_true",
+                       help="demo.py / test.py: per image <stem>_rle.json under <save_dir>/instances/, the live instances "
+                            "with their masks as COCO run-length strings, encoded on the GPU; test.py also collects "
+                            "<save_dir>/results_segm.json (COCO segm results); with --track also "
+                            "instances/mots/<sequence>.txt (MOTS text format); not for the synthetic set")
+        p.add_argument("--mots_class_map", default="",
+                       help="--track --save_rle: label id : class id pairs of the MOTS file, e.g. 26:1,24:2 (KITTI MOTS "
+                            "car and pedestrian); a label the map lacks is left out; empty: the label ids themselves")
         p.add_argument("--pixel_iou", action="store_true",
                        help="test.py: also score every image's label map (detector.instances) at pixel level on the "
                             "GPU: class and category IoU and instance-weighted iIoU, the confusion matrix; needs "
@@ -268,6 +276,14 @@ class opts(object):
                                  if opt.dataset == "synthetic" else
                                  "cityscapes_panoptic_<split>.json is the Cityscapes format and carries Cityscapes label "
                                  "ids, which this data set's instances do not have"))
+        if opt.save_rle and opt.dataset == "synthetic":
+            self.parser.error("--save_rle draws with a data set's result writer; the synthetic set has none (use "
+                              "cityscapes, kitti_poly or IDD)")
+        try:
+            from .detectors.tracking import parse_class_map
+            opt.mots_classes = parse_class_map(opt.mots_class_map)
+        except ValueError as e:
+            self.parser.error(str(e))
         if not (opt.track_iou == opt.track_iou and 0 < opt.track_iou <= 1):
             self.parser.error("--track_iou must be finite and in (0, 1] (got %r)" % opt.track_iou)
         if opt.track_max_age < 0:

@@ -9,6 +9,8 @@ on the image's own canvas from the detections above --thresh) under `<save_dir>/
 `<stem>_labelIds.png` and `<stem>.json`; `<stem>.txt` and `masks/<stem>_<k>.png`.
 --track takes the sorted frames of the directory as one sequence and links their instances (detectors/tracking.py);
 with --save_ids it also writes `<stem>_trackIds.png` and `<stem>_tracks.json` there.
+--save_rle writes `<stem>_rle.json` there, the live instances with their masks as COCO run-length strings encoded on the
+GPU (utils/rle.py), and with --track the sequence's MOTS text file `mots/<the directory's path, joined by _>.txt`.
 There is no video decoder here: `webcam` and video files are refused."""
 import os
 import sys
@@ -53,22 +55,29 @@ def demo(opt):
     if getattr(opt, "track", False):
         from centerpoly_amd.detectors import tracking
         seq = tracking.SequenceTracker(opt.track_iou, opt.track_max_age)
+    save_rle, mots_files = getattr(opt, "save_rle", False), None
     for name in names:
         ret = detector.run(name)
         print("".join("{} {:.3f}s |".format(stat, ret[stat]) for stat in time_stats)
               + "vis {:.3f}s |".format(ret["vis_time"]))
-        if opt.save_ids or opt.save_masks or seq is not None:
+        if opt.save_ids or opt.save_masks or save_rle or seq is not None:
             from centerpoly_amd.detectors import instances
             maps = detector.instances(ret["results"])
             inst_dir, stem = os.path.join(opt.save_dir, "instances"), instances.image_stem(name)
             if seq is not None:                                  # the directory is one sequence
-                ret["tracked"] = seq.step(os.path.join(os.path.dirname(name), "frame"), maps)[1]
+                key, ret["tracked"] = seq.step(os.path.join(os.path.dirname(name), "frame"), maps)
+                if save_rle:
+                    if mots_files is None:
+                        mots_files = tracking.MotsWriter(inst_dir, getattr(opt, "mots_classes", None))
+                    mots_files.add(key, maps, ret["tracked"], stem)
                 if opt.save_ids:
                     tracking.save_tracks(maps, ret["tracked"], inst_dir, stem)
             if opt.save_ids:
                 instances.save_ids(maps, inst_dir, stem)
             if opt.save_masks:
                 instances.save_masks(maps, inst_dir, stem)
+            if save_rle:
+                instances.save_rle(maps, inst_dir, stem)
         if getattr(opt, "save_panoptic", False):
             from centerpoly_amd.datasets.evaluation import panoptic
             from centerpoly_amd.detectors import instances

@@ -57,7 +57,8 @@ extern "C" {
                               cp_conv1x1_stream_*, cp_conv3x3_stream_*, cp_instance_map(_workspace_bytes),
                               cp_pixel_confusion(_workspace_bytes), cp_panoptic_pairs(_workspace_bytes), cp_panoptic_match,
                               cp_boundary_overlaps(_workspace_bytes), cp_polygon_overlaps(_workspace_bytes),
-                              cp_merge_detections_mask(_workspace_bytes), cp_map_pairs, cp_track_associate, cp_track_update */
+                              cp_merge_detections_mask(_workspace_bytes), cp_map_pairs, cp_track_associate, cp_track_update,
+                              cp_rle_encode(_workspace_bytes), cp_rle_decode(_workspace_bytes) */
 
 enum {
   CP_OK = 0,
@@ -766,6 +767,58 @@ int cp_track_associate(const int32_t* pairs, int32_t n, const int32_t* label, co
 int cp_track_update(const uint8_t* index, int32_t n, const int32_t* label, int32_t H, int32_t W, const int32_t* slots,
                     const int32_t* inst, const uint8_t* assigned, const int32_t* status, int32_t multiplier,
                     uint16_t* mem, int32_t* ids, void* stream);
+
+/* ------------------------------------------------ run-length masks (utils/rle.py) --
+ * COCO's run-length encoding of binary masks, {"size": [H, W], "counts": "<string>"}, encoded from and decoded to device
+ * masks.  Not in the reference tree, and no COCO library is part of this project: the format is restated here from the
+ * published algorithm and pinned by the literal host statement tests/golden/rle_host.py.
+ *
+ * Counts.  A pixel of M[H][W] is set when its byte is non-zero.  Read the pixels in column-major order, j = x * H + y,
+ * starting from an imagined value 0 before j = 0.  cnts[0] is the number of leading zeros (0 when pixel (0, 0) is set),
+ * cnts[1] the length of the following run of ones, and so on alternating; the last run ends at H * W.  So
+ * sum(cnts) == H * W, the odd entries sum to the area, and m = changes + 1.
+ * String.  For i = 0 .. m - 1: x = cnts[i], and for i > 2, x -= cnts[i - 2] (signed).  Then repeat: c = x & 0x1f;
+ * x >>= 5 (arithmetic); more = (c & 0x10) ? (x != -1) : (x != 0); if more, c |= 0x20; emit chr(c + 48); until more is
+ * false.  With H * W < 2^31 a number takes 1 .. 7 characters.
+ * Parsing a number.  x = 0, k = 0; per character: c = ord(ch) - 48; x |= (c & 0x1f) << 5k; more = c & 0x20; k += 1.
+ * When more is 0 the number ends; if c & 0x10 then, x |= -1 << 5k.  After number i > 2, add cnts[i - 2].
+ *
+ * cp_rle_encode: counts and strings of n masks in one call, six launches whatever n is.
+ *   planes   DEVICE uint8 [n][H][W], non-zero = set, n <= 128      -- exactly one of the two is non-NULL --
+ *   index    DEVICE uint8 [H][W]: mask k is index == k, 1 <= n <= 255 (cp_instance_map's index; 255 = nobody)
+ *   bounds   DEVICE int32 [n][4] inclusive x0, y0, x1, y1, or NULL: the caller promises that mask k is zero outside its
+ *            box (x1 < x0 or y1 < y0, as W, H, -1, -1: empty).  Only the box is read, clipped to the image; column
+ *            x1 + 1, where a mask on the bottom row of column x1 ends, belongs to the work
+ *   counts   DEVICE uint32 [cap_counts] out or NULL: all masks back to back in slot order, mask k at the sum of the m
+ *            before it
+ *   chars    DEVICE bytes [cap_bytes] out: the strings back to back, no terminators (NULL only with cap_bytes == 0)
+ *   table    DEVICE int32 [n][4] out = m, area, byte offset into chars, byte length
+ *   head     DEVICE int32 [4] out = total counts, total bytes, overflow flag, 0
+ * When the total counts (with counts given) or the total bytes exceed their capacity the flag is 1 and nothing is
+ * written at or beyond either capacity; table and head are complete all the same (the lengths are computed from the
+ * masks, not from stored counts), so a second call can be sized from them.  Values beyond int32 saturate.
+ * H * W >= 2^31, n > 128 with planes, n > 255 with index: CP_EUNSUPPORTED; both or neither of planes and index, n < 1,
+ * non-positive H or W, a negative capacity, null table, head or (with cap_bytes > 0) chars, misaligned tables:
+ * CP_EINVAL; workspace NULL or shorter than cp_rle_encode_workspace_bytes: CP_EWORKSPACE (24 bytes per mask, column and
+ * row segment, 8 segments: n * W * 192 bytes and the per-mask records, of which only the columns of a mask's box are
+ * touched; it does not depend on cap_counts, which the query takes for the caller's convenience; 16-byte aligned).  All checks come before any device work.  Any H, W and
+ * alignment of the masks.  No atomics: the same bits on every run.
+ *
+ * cp_rle_decode: n planes from counts.
+ *   counts   DEVICE uint32: the counts of all masks      table  HOST int32 [n][2] = offset into counts and m per mask
+ *   value    0 .. 255, the byte of a set pixel             planes DEVICE uint8 [n][H][W] out, every byte written
+ *   status   DEVICE int32 [n] out: 0, or 1 with an all-zero plane when sum(cnts) != H * W (so also when a running sum
+ *            passes H * W, or m == 0).  Counts of zero are legal anywhere.
+ * 1 <= n <= 255, H * W < 2^31 (CP_EUNSUPPORTED beyond); null table, planes, status or (with any m > 0) counts, a
+ * negative offset or m, value outside 0 .. 255: CP_EINVAL; workspace NULL or shorter than
+ * cp_rle_decode_workspace_bytes(n, max(offset + m)) (the run ends, 4 bytes a count): CP_EWORKSPACE.  Two launches. */
+size_t cp_rle_encode_workspace_bytes(int32_t n, int32_t H, int32_t W, int64_t cap_counts);
+int cp_rle_encode(const uint8_t* planes, const uint8_t* index, int32_t n, int32_t H, int32_t W, const int32_t* bounds,
+                  uint32_t* counts, int64_t cap_counts, uint8_t* chars, int64_t cap_bytes, int32_t* table, int32_t* head,
+                  void* workspace, size_t workspace_bytes, void* stream);
+size_t cp_rle_decode_workspace_bytes(int32_t n, int64_t total_counts);
+int cp_rle_decode(const uint32_t* counts, const int32_t* table, int32_t n, int32_t H, int32_t W, int32_t value,
+                  uint8_t* planes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------ boundary evaluation (evaluation/boundary.py) --
  * cp_boundary_overlaps: the pixel counting of Boundary IoU / Boundary AP (Cheng et al., CVPR 2021) for ONE image --

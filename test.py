@@ -22,7 +22,11 @@ through an instance tracker (detectors/tracking.py) that starts anew where the s
 plus `<city>_<seq>` of `<city>_<seq>_<frame>` names); --save_ids then also writes `<stem>_trackIds.png` and
 `<stem>_tracks.json`, and with --gt_dir -- whose instance ids must then be consistent over a sequence -- the MOTS
 measures (evaluation/tracking.py) are printed after the other tables, resultTracking.json is written and the dict gains
-"tracking".  `--dataset synthetic`
+"tracking".  With --save_rle every image's live instances also go to
+`<save_dir>/instances/<stem>_rle.json` with their masks as COCO run-length strings, encoded on the device
+(utils/rle.py), all of them are collected in `<save_dir>/results_segm.json` (COCO segm results: image_id, category_id,
+score, bbox, segmentation), and with --track the frames' owned pixels go to `instances/mots/<sequence>.txt` in the MOTS
+text format (--mots_class_map picks and renames the classes).  `--dataset synthetic`
 feeds hash-generated uint8 arrays (no files)."""
 import os
 import sys
@@ -71,6 +75,7 @@ def run_test(opt, evaluate=True):
         return per_image
 
     save_ids, save_masks = getattr(opt, "save_ids", False), getattr(opt, "save_masks", False)
+    save_rle, segm = getattr(opt, "save_rle", False), []
     inst_dir = os.path.join(opt.save_dir, "instances")
 
     def instances_stem(file_name):
@@ -86,10 +91,19 @@ def run_test(opt, evaluate=True):
         if save_masks:
             instances.save_masks(maps, inst_dir, stem)
 
+    def save_rle_instances(item, file_name, maps, rows):
+        """--save_rle: <stem>_rle.json, and the image's entries of results_segm.json (the class and the score are the
+        source row's)."""
+        from centerpoly_amd.detectors import instances
+        for _, e in instances.save_rle(maps, inst_dir, instances.image_stem(file_name))[1]:
+            row = rows[e["source_row"]]
+            segm.append({"image_id": int(item["img_id"]), "category_id": int(dataset._valid_ids[int(row[5])]),
+                         "score": float(row[4]), "bbox": e["bbox"], "segmentation": e["segmentation"]})
+
     if opt.dataset == "synthetic":
-        if save_ids or save_masks:
-            raise ValueError("--save_ids / --save_masks draw with a data set's result writer; the synthetic set has "
-                             "none (use cityscapes, kitti_poly or IDD)")
+        if save_ids or save_masks or save_rle:
+            raise ValueError("--save_ids / --save_masks / --save_rle draw with a data set's result writer; the synthetic "
+                             "set has none (use cityscapes, kitti_poly or IDD)")
         synthetic =((ind, (synth.uniform("test/img%d" % ind, (opt.input_h, opt.input_w, 3)) * 255).astype(np.uint8))
                      for ind in range(len(dataset)))
         for items in eval_images.group(({"img_id": ind, "image": img} for ind, img in synthetic), batch_size, same_size):
@@ -136,6 +150,7 @@ def run_test(opt, evaluate=True):
     if getattr(opt, "track", False):
         from centerpoly_amd.detectors import tracking
         seq = tracking.SequenceTracker(opt.track_iou, opt.track_max_age)
+        mots_files = tracking.MotsWriter(inst_dir, getattr(opt, "mots_classes", None)) if save_rle else None
         if evaluator is not None:
             from centerpoly_amd.datasets.evaluation import tracking as mots_eval
             mots = mots_eval.TrackingEvaluator(protocol, opt.track_ignore_id)
@@ -155,15 +170,19 @@ def run_test(opt, evaluate=True):
                     extra["distances"] = (item["disparity"], item["camera"])
                 dataset.score_instances_device(detector.device_rows(res, image=b), item["gt_ids"], item["gt_table"],
                                                evaluator, **extra)
-            if save_ids or save_masks or pixel is not None or pan is not None or save_pan or seq is not None:
+            if save_ids or save_masks or save_rle or pixel is not None or pan is not None or save_pan or seq is not None:
                 file_name = dataset.coco.loadImgs(ids=[item["img_id"]])[0]["file_name"]
                 maps = detector.instances(res, image=b)                    # once for the files and the score
                 if save_ids or save_masks:
                     save_instances(file_name, maps)
+                if save_rle:
+                    save_rle_instances(item, file_name, maps, detector.host_rows(res, image=b))
                 if seq is not None:                                        # step per image, in the loader's order
                     key, tracked = seq.step(file_name, maps)
                     if save_ids:
                         tracking.save_tracks(maps, tracked, inst_dir, instances_stem(file_name))
+                    if mots_files is not None:
+                        mots_files.add(key, maps, tracked, instances_stem(file_name))
                     if mots is not None:
                         mots.add_maps(key, maps, tracked, item["gt_ids"], file_name)
                 if pixel is not None:
@@ -176,6 +195,10 @@ def run_test(opt, evaluate=True):
                     pan_entries.append(pan_files.save_panoptic(maps, pan_dir, instances.image_stem(file_name)))
             stamps.append(time.time())
         print("[{}/{}] ".format(ind, len(images)) + " ".join("|{} {:.3f}s".format(t, avg[t].avg) for t in avg))
+    if save_rle:
+        import json
+        with open(os.path.join(opt.save_dir, "results_segm.json"), "w") as f:
+            json.dump(segm, f)
     if not evaluate:
         ap = None
     elif evaluator is None:
