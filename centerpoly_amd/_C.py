@@ -121,6 +121,10 @@ _SIGNATURES = {
     "cp_map_pairs": (c_int32, [_P, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P]),
     "cp_track_associate": (c_int32, [_P, c_int32, _P, _P, _P, _P, ctypes.c_double, c_int32, c_int32, _P, _P, _P, _P]),
     "cp_track_update": (c_int32, [_P, c_int32, _P, c_int32, c_int32, _P, _P, _P, _P, c_int32, _P, _P, _P]),
+    "cp_map_pairs_shifted": (c_int32, [_P, _P, c_int32, _P, c_int32, c_int32, c_int32, _P, _P]),
+    "cp_track_predict": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P]),
+    "cp_track_kinematics_workspace_bytes": (c_size_t, [c_int32]),
+    "cp_track_kinematics": (c_int32, [_P, c_int32, c_int32, c_int32, _P, _P, _P, c_int32, _P, _P, c_size_t, _P]),
     "cp_rle_encode_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int64]),
     "cp_rle_encode": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "cp_rle_decode_workspace_bytes": (c_size_t, [c_int32, c_int64]),

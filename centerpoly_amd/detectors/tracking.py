@@ -4,7 +4,12 @@ include/centerpoly_hip.h, pinned by tests/golden/tracking_host.py; not in the re
 A tracker belongs to one canvas and keeps its memory map and slot table on the device.  A step issues three calls on
 the current stream -- cp_map_pairs (memory map against the frame's owner map), cp_track_associate (greedy matching, new
 tracks, ageing, one workgroup) and cp_track_update (the new memory map and the id image) -- and one copy brings the small
-tables back.  The defaults iou_thresh = 0.3 and max_age = 0 are this project's untuned choices."""
+tables back.  The defaults iou_thresh = 0.3 and max_age = 0 are this project's untuned choices.
+
+With motion=True ("instance tracking with motion", pinned by tests/golden/tracking_motion_host.py) a track's remembered
+pixels are compared where the track should be now, at the velocity between its last two sightings: the step is
+cp_track_predict, cp_map_pairs_shifted, cp_track_associate, cp_track_kinematics, cp_track_update.  The velocity is not
+smoothed: that, too, is an untuned choice."""
 import ctypes
 import math
 import os
@@ -25,6 +30,11 @@ O_STATUS = O_NEXT + 1
 O_INST = O_STATUS + 1
 O_ASSIGNED = O_INST + MAX_INSTANCES * 5
 STATE_INTS = O_ASSIGNED + SLOTS // 4
+# behind them under motion: kin [256][6] = {cx, cy, vx, vy, seen, valid} (1/16 pixel), shift [256][2] = {dx, dy}
+O_KIN = STATE_INTS
+O_SHIFT = O_KIN + SLOTS * 6
+MOTION_INTS = O_SHIFT + SLOTS * 2
+SUBPIXEL = 16.0
 
 
 def _host_ptr(a):
@@ -60,6 +70,29 @@ def map_pairs(a, b, R, n, row_of=None, out=None):
         out = torch.empty((cells,), dtype=torch.int32, device=a.device)
     _C.check(_C.lib().cp_map_pairs(_C.ptr(a), _C.ptr(row_of), R, _C.ptr(b), n, H, W, _C.ptr(out), _C.stream()),
              "cp_map_pairs")
+    return out[:cells].view(R + 1, n + 1)
+
+
+def map_pairs_shifted(a, shift, b, R, n, out=None):
+    """cp_map_pairs_shifted on device tensors: a 16-bit [H, W], shift int32 [R, 2] = (dx, dy) per row, b uint8 [H, W].
+    Returns the device table int32 [R + 1, n + 1] (a view of `out` when given): row r counts the pixels of r moved by
+    its shift and clipped to the canvas, row R is what is left of every column's area (it may be negative)."""
+    a = as_bits16(a)
+    if a.dim() != 2 or b.dim() != 2 or b.dtype != torch.uint8 or tuple(a.shape) != tuple(b.shape):
+        raise ValueError("map_pairs_shifted takes a 16-bit map and a uint8 map of one shape [H, W], got %s %s and %s %s"
+                         % (a.dtype, tuple(a.shape), b.dtype, tuple(b.shape)))
+    R, n = int(R), int(n)
+    if not (0 <= R <= MAX_ROWS and 0 <= n <= MAX_COLS):
+        raise ValueError("map_pairs_shifted: R = %d rows (at most %d), n = %d columns (at most %d)"
+                         % (R, MAX_ROWS, n, MAX_COLS))
+    if shift.dtype != torch.int32 or shift.numel() != 2 * R:
+        raise ValueError("shift must be int32 [%d, 2], got %s %s" % (R, shift.dtype, tuple(shift.shape)))
+    H, W = (int(v) for v in a.shape)
+    cells = (R + 1) * (n + 1)
+    if out is None:
+        out = torch.empty((cells,), dtype=torch.int32, device=a.device)
+    _C.check(_C.lib().cp_map_pairs_shifted(_C.ptr(a), _C.ptr(shift) if R else None, R, _C.ptr(b), n, H, W, _C.ptr(out),
+                                           _C.stream()), "cp_map_pairs_shifted")
     return out[:cells].view(R + 1, n + 1)
 
 
@@ -120,7 +153,9 @@ class TrackedFrame(object):
                          n instances; slot -1 for a dead instance, inter = union = 0 for a new track), alive (int
                          [A, 6] rows slot, track_id, label, first_frame, last_seen, hits of the occupied slots), slots
                          (the whole table [256, 5]), assigned ([256], slots that took an instance in this frame),
-                         next_id, status
+                         next_id, status; under motion also kin ([256, 6], after the step), shift ([256, 2], the
+                         shifts used in this frame), centroid and velocity ([n, 2] float pixels and pixels per frame
+                         of the instance's track, kin / 16; zeros for a dead instance)
       frame              the frame counter t of this step; multiplier"""
 
     def __init__(self, ids, track_of_instance, table, frame, multiplier):
@@ -130,7 +165,7 @@ class TrackedFrame(object):
 class InstanceTracker(object):
     """InstanceTracker(canvas = (width, height)).step(maps) for the InstanceMaps of consecutive frames."""
 
-    def __init__(self, canvas, iou_thresh=0.3, max_age=0, multiplier=None, device=None):
+    def __init__(self, canvas, iou_thresh=0.3, max_age=0, multiplier=None, device=None, motion=False):
         W, H = (int(v) for v in canvas)
         if W < 1 or H < 1:
             raise ValueError("the canvas must be at least 1 x 1 (width, height), got %r" % (canvas,))
@@ -139,18 +174,22 @@ class InstanceTracker(object):
             raise ValueError("multiplier must be >= 1, got %r" % (multiplier,))
         self.canvas, self.iou_thresh, self.max_age = (W, H), float(iou_thresh), int(max_age)
         self.multiplier = None if multiplier is None else int(multiplier)
+        self.motion = bool(motion)
         self.device = torch.device(device if device is not None else "cuda")
         if self.device.type != "cuda":
             raise _C.NativeError("InstanceTracker needs a HIP device (got %s); there is no CPU fallback" % self.device)
         _C.lib()
         self.pairs = torch.empty(((SLOTS + 1) * (MAX_INSTANCES + 1),), dtype=torch.int32, device=self.device)
+        if self.motion:
+            self.moments_bytes = int(_C.lib().cp_track_kinematics_workspace_bytes(MAX_INSTANCES))
+            self.moments = _C.workspace(self.moments_bytes, self.device)
         self.reset()
 
     def reset(self):
         """Forget every track: the state of a new tracker."""
         W, H = self.canvas
         self.mem = torch.full((H, W), -1, dtype=torch.int16, device=self.device)       # 0xffff
-        host = np.zeros((STATE_INTS,), np.int32)
+        host = np.zeros((MOTION_INTS if self.motion else STATE_INTS,), np.int32)
         host[O_NEXT] = 1
         self.state = torch.from_numpy(host).to(self.device)
         self.frame = 0
@@ -165,13 +204,22 @@ class InstanceTracker(object):
                                maps.multiplier if self.multiplier is None else self.multiplier)
 
     def enqueue(self, index, n, label, live, multiplier):
-        """The three calls of a step for frame `self.frame`, nothing read back and the frame counter left alone: the id
-        image.  Arguments as _instances returns them; step_index is the checked way in."""
+        """The three calls of a step for frame `self.frame` (five under motion), nothing read back and the frame
+        counter left alone: the id image.  Arguments as _instances returns them; step_index is the checked way in."""
         W, H = self.canvas
-        pairs = map_pairs(self.mem, index, SLOTS, n, out=self.pairs)
-        _associate(self.state, pairs, n, label, live, self.iou_thresh, self.max_age, self.frame)
-        ids = torch.empty((H, W), dtype=torch.int32, device=self.device)
         at = lambda o: ctypes.c_void_p(self.state.data_ptr() + 4 * o)     # noqa: E731
+        if self.motion:
+            _C.check(_C.lib().cp_track_predict(at(0), at(O_KIN), int(self.frame), H, W, at(O_SHIFT), _C.stream()),
+                     "cp_track_predict")
+            pairs = map_pairs_shifted(self.mem, self.state[O_SHIFT:O_SHIFT + 2 * SLOTS], index, SLOTS, n, out=self.pairs)
+        else:
+            pairs = map_pairs(self.mem, index, SLOTS, n, out=self.pairs)
+        _associate(self.state, pairs, n, label, live, self.iou_thresh, self.max_age, self.frame)
+        if self.motion:
+            _C.check(_C.lib().cp_track_kinematics(_C.ptr(index), n, H, W, at(O_INST), at(0), at(O_STATUS),
+                                                  int(self.frame), at(O_KIN), _C.ptr(self.moments), self.moments_bytes,
+                                                  _C.stream()), "cp_track_kinematics")
+        ids = torch.empty((H, W), dtype=torch.int32, device=self.device)
         _C.check(_C.lib().cp_track_update(_C.ptr(index), n, _host_ptr(label) if n else None, H, W, at(0), at(O_INST),
                                           at(O_ASSIGNED), at(O_STATUS), multiplier, _C.ptr(self.mem), _C.ptr(ids),
                                           _C.stream()), "cp_track_update")
@@ -193,7 +241,8 @@ class InstanceTracker(object):
         n, label, live = _instances(n, label, live)
         ids = self.enqueue(index.contiguous(), n, label, live, int(multiplier))
         track_of_instance = self.state[O_INST:O_INST + 5 * n].view(n, 5)[:, 1].clone()
-        tab = _split_state(self.state.cpu().numpy(), n)                   # the one copy
+        host = self.state.cpu().numpy()                                   # the one copy
+        tab = _split_state(host, n)
         if tab["status"]:
             raise ValueError("%s in frame %d: the step changed nothing; lower --track_max_age or raise --thresh"
                              % (TOO_MANY, self.frame))
@@ -201,13 +250,19 @@ class InstanceTracker(object):
         occupied = np.flatnonzero(slots[:, 0])
         tab.update({"n": n, "slot": inst[:, 0], "track_id": inst[:, 1], "inter": inst[:, 2], "union": inst[:, 3],
                     "is_new": inst[:, 4] != 0, "alive": np.concatenate([occupied[:, None], slots[occupied]], 1)})
+        if self.motion:
+            kin = host[O_KIN:O_SHIFT].reshape(SLOTS, 6).copy()
+            of_inst = np.where(inst[:, :1] >= 0, kin[np.maximum(inst[:, 0], 0)], 0) / SUBPIXEL
+            tab.update({"kin": kin, "shift": host[O_SHIFT:MOTION_INTS].reshape(SLOTS, 2).copy(),
+                        "centroid": of_inst[:, 0:2], "velocity": of_inst[:, 2:4]})
         frame = self.frame
         self.frame += 1
         return TrackedFrame(ids, track_of_instance, tab, frame, int(multiplier))
 
 
 def save_tracks(maps, tracked, out_dir, stem):
-    """--track --save_ids: `<stem>_tracks.json` (per live instance: track id, label, score, box, is_new) and
+    """--track --save_ids: `<stem>_tracks.json` (per live instance: track id, label, score, box, is_new; under
+    --track_motion also centroid [x, y] in pixels and velocity [vx, vy] in pixels per frame of its track) and
     `<stem>_trackIds.png` (16 bit, label * multiplier + track_id) in out_dir.  The PNG cannot hold a track id that
     reaches the multiplier: a ValueError that names the frame; the JSON has no such limit and is written first.
     Returns the two paths."""
@@ -222,6 +277,10 @@ def save_tracks(maps, tracked, out_dir, stem):
                 "class_name": maps.names.get(int(t["label"][k]), ""), "score": float(t["score"][k]),
                 "box": [int(v) for v in t["box"][k]], "is_new": bool(k_tab["is_new"][k])}
                for k in range(int(t["n"])) if t["live"][k]]
+    if "centroid" in k_tab:
+        for e, k in zip(entries, [k for k in range(int(t["n"])) if t["live"][k]]):
+            e["centroid"] = [float(v) for v in k_tab["centroid"][k]]
+            e["velocity"] = [float(v) for v in k_tab["velocity"][k]]
     with open(paths[0], "w") as f:
         json.dump({"frame": int(tracked.frame), "width": maps.canvas[0], "height": maps.canvas[1],
                    "multiplier": int(tracked.multiplier), "instances": entries}, f)
@@ -309,8 +368,8 @@ class SequenceTracker(object):
     """The drivers' tracker: frames arrive in order with their file names, the tracker starts anew where the sequence
     key (evaluation.tracking.sequence_key) changes, on a tracker of the frame's canvas."""
 
-    def __init__(self, iou_thresh=0.3, max_age=0):
-        self.iou_thresh, self.max_age = iou_thresh, max_age
+    def __init__(self, iou_thresh=0.3, max_age=0, motion=False):
+        self.iou_thresh, self.max_age, self.motion = iou_thresh, max_age, bool(motion)
         self.tracker, self.key = None, None
 
     def step(self, file_name, maps):
@@ -320,7 +379,8 @@ class SequenceTracker(object):
         if key != self.key:
             if self.tracker is None or self.tracker.canvas != tuple(maps.canvas) or \
                     self.tracker.device != maps.index.device:
-                self.tracker = InstanceTracker(maps.canvas, self.iou_thresh, self.max_age, device=maps.index.device)
+                self.tracker = InstanceTracker(maps.canvas, self.iou_thresh, self.max_age, device=maps.index.device,
+                                               motion=self.motion)
             else:
                 self.tracker.reset()
             self.key = key

@@ -175,6 +175,12 @@ class opts(object):
         p.add_argument("--track_max_age", type=int, default=0,
                        help="--track: frames a track may go unseen before it ends, >= 0; 0 (a track not seen in a frame "
                             "ends there) is this project's untuned choice")
+        p.add_argument("--track_motion", action="store_true",
+                       help="--track: compare a track's remembered pixels where the track should be now, moved at the "
+                            "velocity between its last two sightings (constant velocity, no smoothing: untuned), on "
+                            "the GPU; needs --track and pays off with --track_max_age > 0, where an object that was "
+                            "hidden for some frames returns displaced; with --save_ids <stem>_tracks.json also holds "
+                            "every track's centroid and velocity")
         p.add_argument("--track_ignore_id", type=int, default=10000,
                        help="--track with --gt_dir: the ground-truth id of the ignore region (10000 in KITTI MOTS)")
         p.add_argument("--not_prefetch_test", action="store_true")
@@ -288,6 +294,8 @@ class opts(object):
             self.parser.error("--track_iou must be finite and in (0, 1] (got %r)" % opt.track_iou)
         if opt.track_max_age < 0:
             self.parser.error("--track_max_age must be at least 0 (got %d)" % opt.track_max_age)
+        if opt.track_motion and not opt.track:
+            self.parser.error("--track_motion predicts the tracks of --track: give --track as well")
         if opt.track:
             if opt.dataset == "synthetic":
                 self.parser.error("--track links the instance maps a data set's result writer draws; dataset "

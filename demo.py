@@ -54,7 +54,7 @@ def demo(opt):
     seq = None
     if getattr(opt, "track", False):
         from centerpoly_amd.detectors import tracking
-        seq = tracking.SequenceTracker(opt.track_iou, opt.track_max_age)
+        seq = tracking.SequenceTracker(opt.track_iou, opt.track_max_age, getattr(opt, "track_motion", False))
     save_rle, mots_files = getattr(opt, "save_rle", False), None
     for name in names:
         ret = detector.run(name)

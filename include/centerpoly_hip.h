@@ -58,7 +58,8 @@ extern "C" {
                               cp_pixel_confusion(_workspace_bytes), cp_panoptic_pairs(_workspace_bytes), cp_panoptic_match,
                               cp_boundary_overlaps(_workspace_bytes), cp_polygon_overlaps(_workspace_bytes),
                               cp_merge_detections_mask(_workspace_bytes), cp_map_pairs, cp_track_associate, cp_track_update,
-                              cp_rle_encode(_workspace_bytes), cp_rle_decode(_workspace_bytes) */
+                              cp_rle_encode(_workspace_bytes), cp_rle_decode(_workspace_bytes), cp_map_pairs_shifted,
+                              cp_track_predict, cp_track_kinematics(_workspace_bytes) */
 
 enum {
   CP_OK = 0,
@@ -767,6 +768,64 @@ int cp_track_associate(const int32_t* pairs, int32_t n, const int32_t* label, co
 int cp_track_update(const uint8_t* index, int32_t n, const int32_t* label, int32_t H, int32_t W, const int32_t* slots,
                     const int32_t* inst, const uint8_t* assigned, const int32_t* status, int32_t multiplier,
                     uint16_t* mem, int32_t* ids, void* stream);
+
+/* ------------------------------------------------ instance tracking with motion (detectors/tracking.py, motion=True) --
+ * The same tracker with every track's remembered pixels moved to where the track should be now, at constant velocity
+ * (as SORT does for boxes), before they are compared with the frame.  Not in the reference tree: this project's rule,
+ * pinned by the host statement tests/golden/tracking_motion_host.py.  All quantities are integers; positions and
+ * velocities are in 1/16 pixel; every product and quotient below is computed in 64 bits.
+ *
+ * Beside mem, slots and next_id the tracker keeps
+ *   kin     int32 [CP_TRACK_SLOTS][6] = {cx, cy, vx, vy, seen, valid}, all zero for a new tracker
+ * and a step at frame t is
+ *   1. predict (cp_track_predict).  For a slot with track_id != 0 and valid: g = t - seen,
+ *      dx = clamp(floor((vx * g + 8) / 16), -W, W), dy = clamp(floor((vy * g + 8) / 16), -H, H) (floor division: round
+ *      half up); (0, 0) for every other slot.
+ *   2. shifted counts (cp_map_pairs_shifted with R = CP_TRACK_SLOTS).  For every pixel (x, y) with s = mem[y][x] < R:
+ *      q = (x + dx[s], y + dy[s]); if q lies on the canvas pairs[s][c] += 1 with c = index[q] when that is < n, else n;
+ *      a pixel whose q is off the canvas is counted nowhere (the predicted footprint is clipped).  Row R, column k =
+ *      area_cur[k] - the sum of pairs[s][k] over s < R, with area_cur[k] the pixels with index == k (k = n: index >= n).
+ *      Row R may be negative: two predictions may land on the same pixels.  The row sum of s is its clipped predicted
+ *      area and every column sum is the instance's true area, which is all cp_track_associate reads beside the cells:
+ *      IoU = inter / (predicted area + area_cur - inter).  With all shifts zero the table is cp_map_pairs' bit for bit.
+ *   3. cp_track_associate, unchanged.
+ *   4. kinematics (cp_track_kinematics).  With A, Sx, Sy the pixel count and the sums of x and y over index == k:
+ *      cx = floor((32 * Sx + A) / (2 * A)), cy likewise.  For every instance k with inst[k].slot = s >= 0:
+ *        A == 0 and is_new               kin[s] = 0
+ *        A == 0 and not new              kin[s] stays (a match needs inter > 0, so this does not happen)
+ *        is_new, or kin[s].valid == 0    kin[s] = {cx, cy, 0, 0, t, 1}
+ *        otherwise                       g = t - kin[s].seen, v = (c - c_old) / g rounded toward zero per axis,
+ *                                        kin[s] = {cx, cy, vx, vy, t, 1}
+ *      The velocity is the one between the last two sightings, without smoothing.  Afterwards every slot with
+ *      track_id == 0 has kin[s] = 0.  With status[0] != 0 nothing in kin changes.
+ *   5. cp_track_update, unchanged.  A lost track's remembered pixels stay where they were at frame kin.seen, which is
+ *      why the shift of step 1 grows with g.
+ *
+ * cp_map_pairs_shifted: cp_map_pairs without the lookup and with a shift per row.
+ *   shift   DEVICE int32 [R][2] = {dx, dy}, any values (NULL only with R == 0)
+ * Limits and codes are cp_map_pairs': R > 1024, n > 255, H * W >= 2^31: CP_EUNSUPPORTED; null a, b, pairs or shift,
+ * non-positive H or W, negative R or n, a misaligned table: CP_EINVAL; all checks come before any device work.  Any H,
+ * any W, any alignment of a and b.  Two launches: the clear, then one pass that streams a and b (which gives area_cur)
+ * and gathers b at the shifted positions -- 16 contiguous bytes at whatever byte offset for a piece of 16 pixels of one
+ * image row that all belong to one slot and land on the canvas, a byte per pixel for every other piece that holds a
+ * track.  The workgroup's table lives in LDS up to 33153 cells and in the global table beyond.  Integer atomics only.
+ *
+ * cp_track_predict: step 1 for the CP_TRACK_SLOTS rows, one launch.  shift DEVICE int32 [CP_TRACK_SLOTS][2] out.  Null or
+ * misaligned tables, non-positive H or W, t < 0: CP_EINVAL.
+ *
+ * cp_track_kinematics: step 4 from the tables cp_track_associate wrote.  One memset, one streaming pass over index
+ * ({A, Sx, Sy} per instance in 64-bit integers) and one launch of one workgroup for the table.
+ *   workspace  DEVICE, 8-byte aligned, cp_track_kinematics_workspace_bytes(n) (24 bytes an instance; none for n == 0)
+ * n > 128, H * W >= 2^31, H or W > 2^26 (16 * x must fit 32 bits): CP_EUNSUPPORTED; null or misaligned tables,
+ * non-positive H or W, negative n or t: CP_EINVAL; a null or shorter workspace: CP_EWORKSPACE. */
+int cp_map_pairs_shifted(const uint16_t* a, const int32_t* shift, int32_t R, const uint8_t* b, int32_t n, int32_t H,
+                         int32_t W, int32_t* pairs, void* stream);
+int cp_track_predict(const int32_t* slots, const int32_t* kin, int32_t t, int32_t H, int32_t W, int32_t* shift,
+                     void* stream);
+size_t cp_track_kinematics_workspace_bytes(int32_t n);
+int cp_track_kinematics(const uint8_t* index, int32_t n, int32_t H, int32_t W, const int32_t* inst, const int32_t* slots,
+                        const int32_t* status, int32_t t, int32_t* kin, void* workspace, size_t workspace_bytes,
+                        void* stream);
 
 /* ------------------------------------------------ run-length masks (utils/rle.py) --
  * COCO's run-length encoding of binary masks, {"size": [H, W], "counts": "<string>"}, encoded from and decoded to device

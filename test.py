@@ -149,7 +149,7 @@ def run_test(opt, evaluate=True):
     seq = mots = None
     if getattr(opt, "track", False):
         from centerpoly_amd.detectors import tracking
-        seq = tracking.SequenceTracker(opt.track_iou, opt.track_max_age)
+        seq = tracking.SequenceTracker(opt.track_iou, opt.track_max_age, getattr(opt, "track_motion", False))
         mots_files = tracking.MotsWriter(inst_dir, getattr(opt, "mots_classes", None)) if save_rle else None
         if evaluator is not None:
             from centerpoly_amd.datasets.evaluation import tracking as mots_eval
