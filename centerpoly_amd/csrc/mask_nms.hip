@@ -20,14 +20,16 @@
 //           intersection of the two boxes, a wave reduction, one lane stores both cells; the diagonal takes area[i].
 //           Every other pair exits at once;
 //   select  one wave per class, scores, areas and candidate indices in LDS: the arg-max is the 64-bit-key DPP idiom of
-//           merge_nms.hip, the chosen candidate's line of `inter` is read once per iteration, the decay pass leaves
+//           row_merge.h, the chosen candidate's line of `inter` is read once per iteration, the decay pass leaves
 //           the next iteration's keys behind;
 //   cut     one workgroup: merge_outputs' rule on the kept rows (rank counting in LDS), a prefix sum, the whole-row
 //           copy.
+// The class rule, the partition, the arg-max's order and the cut are row_merge.h's, shared with merge_nms.hip.
 // Integer atomics and vector stores only: a call repeats its bits.
 #include <math.h>
 
 #include "cp_common.h"
+#include "row_merge.h"
 #include "scanline.h"
 
 #pragma clang fp contract(off)
@@ -37,60 +39,19 @@ namespace {
 constexpr int kMaxRows = 1024;
 constexpr int kMaxClasses = 64;
 constexpr int kMaxVerts = 64;
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / CP_WAVE;
+constexpr int kThreads = row_merge::kThreads;                            // prep and cut: one row per thread
 constexpr int kRowsPerBlock = 4;                                          // waves of the raster kernel's workgroup
 constexpr int kPairsPerBlock = 4;                                         // waves of the pair kernel's workgroup
+static_assert(kMaxRows == kThreads, "mask_prep_kernel and mask_cut_kernel hold one row per thread");
 
-// LDS writes of some lanes become visible to the other lanes of the same wave (which runs in lock-step: no barrier)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// A score and its position in one word whose order is the arg-max's: a higher score wins, then the lower position
-// (-0 and +0 are equal scores).  Every key of a position is above 0, the key of "nothing".
-__device__ __forceinline__ unsigned long long score_key(float s, int pos) {
-  if (s == 0.f) s = 0.f;
-  unsigned u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 32) | (0xffffffffu - (unsigned)pos);
-}
-
-// the largest key of the 64 lanes, in every lane: DPP row shifts and row broadcasts, the result read from lane 63.
-// All 64 lanes are active where this is called.
-template <int CTRL, int ROWS>
-__device__ __forceinline__ unsigned long long max_key_dpp(unsigned long long k) {
-  const int lo = (int)(unsigned)k, hi = (int)(unsigned)(k >> 32);
-  const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, CTRL, ROWS, 0xf, false);
-  const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROWS, 0xf, false);
-  const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
-  return o > k ? o : k;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long k) {
-  k = max_key_dpp<0x111, 0xf>(k);                                         // row_shr:1
-  k = max_key_dpp<0x112, 0xf>(k);                                         // row_shr:2
-  k = max_key_dpp<0x114, 0xf>(k);                                         // row_shr:4
-  k = max_key_dpp<0x118, 0xf>(k);                                         // row_shr:8: lane 15 of a row holds the row's
-  k = max_key_dpp<0x142, 0xa>(k);                                         // row_bcast:15 into rows 1, 3
-  k = max_key_dpp<0x143, 0xc>(k);                                         // row_bcast:31 into rows 2, 3: lane 63 all four
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)k, 63);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(k >> 32), 63);
-  return ((unsigned long long)hi << 32) | lo;
-}
+using row_merge::score_key;
+using row_merge::wave_max_key;
+using row_merge::wave_sync;
 
 __device__ __forceinline__ int wave_sum_i(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
-}
-
-// the class of a row as `cls == j` of the numpy split sees it: -1 when no j of [0, C) equals it
-__device__ __forceinline__ int class_of(float c, int C) {
-  const int ci = (c >= 0.f && c < (float)C) ? (int)c : -1;
-  return ci >= 0 && (float)ci == c ? ci : -1;
 }
 
 struct Box { int w0, w1, y0, y1; };                                       // words and rows, both ends included
@@ -118,11 +79,11 @@ __global__ __launch_bounds__(kThreads) void mask_prep_kernel(MaskArgs a) {
   __shared__ unsigned short s_rank[kMaxRows];                             // position of a row within its class
   __shared__ int s_cnt[kMaxClasses];
   __shared__ int s_start[kMaxClasses];
-  const int t = threadIdx.x, lane = t & (CP_WAVE - 1), wave = t / CP_WAVE;
+  const int t = threadIdx.x;
   int ci = -1;
   if (t < a.R) {
     const float* row = a.rows + (long long)t * a.ncols;
-    ci = class_of(row[5], a.C);
+    ci = row_merge::class_of(row[5], a.C);
     Box b = {1, 0, 1, 0};
     if (ci >= 0) {
       int x0 = INT32_MAX, x1 = INT32_MIN, y0 = INT32_MAX, y1 = INT32_MIN;
@@ -139,30 +100,7 @@ __global__ __launch_bounds__(kThreads) void mask_prep_kernel(MaskArgs a) {
   if (!a.order) return;                                                   // uniform: cp_polygon_overlaps stops here
   if (t < kMaxRows) s_cls[t] = (signed char)ci;
   if (t < a.R) a.sel_idx[t] = -1;
-  __syncthreads();
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (int j = wave; j < a.C; j += kWaves) {                              // one wave per class in turn: the order is fixed
-    int run = 0;
-    for (int r0 = 0; r0 < a.R; r0 += CP_WAVE) {
-      const int r = r0 + lane;
-      const bool mine = r < a.R && s_cls[r] == j;
-      const unsigned long long m = __ballot(mine);
-      if (mine) s_rank[r] = (unsigned short)(run + __popcll(m & below));
-      run += __popcll(m);
-    }
-    if (lane == 0) s_cnt[j] = run;
-  }
-  __syncthreads();
-  if (t == 0) {
-    int acc = 0;
-    for (int j = 0; j < a.C; ++j) {
-      s_start[j] = acc;
-      a.seg_start[j] = acc;
-      a.seg_len[j] = s_cnt[j];
-      acc += s_cnt[j];
-    }
-  }
-  __syncthreads();
+  row_merge::class_partition(s_cls, s_rank, s_cnt, s_start, a.R, a.C, a.seg_start, a.seg_len);
   if (t < a.R && ci >= 0) a.order[s_start[ci] + s_rank[t]] = t;
 }
 
@@ -323,57 +261,18 @@ __global__ __launch_bounds__(CP_WAVE) void mask_select_kernel(MaskArgs a) {
 }
 
 __global__ __launch_bounds__(kThreads) void mask_cut_kernel(MaskArgs a) {
-  __shared__ float s_score[kMaxRows];
-  __shared__ int s_src[kMaxRows];
-  __shared__ int s_excl[kMaxRows + 1];                                    // kept rows before slot r
-  __shared__ int s_wave[kWaves];
-  __shared__ float s_thresh;
-  const int t = threadIdx.x, lane = t & (CP_WAVE - 1), wave = t / CP_WAVE;
-  const int src = t < a.R ? a.sel_idx[t] : -1;
-  const bool valid = src >= 0 && src < a.R;
-  const float sc = valid ? a.sel_score[t] : __builtin_inff();             // an empty slot counts below no score
-  s_score[t] = sc;
-  s_src[t] = src;
-  if (t == 0) { s_thresh = -__builtin_inff(); s_excl[0] = 0; }
-  const int total = __syncthreads_count(valid);
-  const bool cut = total > a.max_per_image;
-  if (cut && valid) {                                                     // np.partition(scores, kth)[kth]
-    const int kth = total - a.max_per_image;
-    int lt = 0, le = 0;
-    for (int j = 0; j < a.R; ++j) {                                       // every lane reads the same address
-      const float w = s_score[j];
-      lt += w < sc ? 1 : 0;
-      le += w <= sc ? 1 : 0;
-    }
-    if (lt <= kth && kth < le) s_thresh = sc;                             // ties write the same value
+  __shared__ row_merge::CutLds<1> s_cut;
+  __shared__ int s_src[kMaxRows];                                         // the source row of slot r, -1: the slot is empty
+  const int t = threadIdx.x;
+  if (t < a.R) {
+    const int src = a.sel_idx[t];
+    s_src[t] = src >= 0 && src < a.R ? src : -1;
   }
   __syncthreads();
-  const int keep = valid && (!cut || sc >= s_thresh) ? 1 : 0;
-  int incl = keep;
-#pragma unroll
-  for (int o = 1; o < CP_WAVE; o <<= 1) {
-    const int up = __shfl_up(incl, o, CP_WAVE);
-    if (lane >= o) incl += up;
-  }
-  if (lane == CP_WAVE - 1) s_wave[wave] = incl;
-  __syncthreads();
-  for (int w = 0; w < wave; ++w) incl += s_wave[w];
-  s_excl[t + 1] = incl;
-  __syncthreads();
-  if (t == 0) a.counts[0] = s_excl[a.R];
-  if (t < a.C) {
-    int s0 = a.seg_start[t], s1 = s0 + a.seg_len[t];
-    s0 = s0 < 0 ? 0 : (s0 > a.R ? a.R : s0);
-    s1 = s1 < s0 ? s0 : (s1 > a.R ? a.R : s1);
-    a.counts[1 + t] = s_excl[s1] - s_excl[s0];
-  }
-  const long long n = (long long)a.R * a.ncols;
-  for (long long e = t; e < n; e += kThreads) {
-    const int r = (int)(e / a.ncols), c = (int)(e - (long long)r * a.ncols);
-    const int d = s_excl[r];
-    if (s_excl[r + 1] != d)
-      a.out[(long long)d * a.ncols + c] = c == 4 ? s_score[r] : a.rows[(long long)s_src[r] * a.ncols + c];
-  }
+  row_merge::cut_rows(
+      s_cut, a.R, [&](int r) { return s_src[r] >= 0; }, [&](int r) { return a.sel_score[r]; },
+      [&](int r) { return a.rows + (long long)s_src[r] * a.ncols; }, a.seg_start, a.seg_len, a.C, a.max_per_image,
+      a.ncols, a.out, a.counts);
 }
 
 // ---- the workspace: the bit planes, then the tables ----

@@ -22,9 +22,11 @@
 // cp_merge_detections: THREE launches (two with nms == 0): a stable partition by class into the workspace (one
 // workgroup; a ballot prefix count per class, no atomics), the soft-NMS kernel above with one wave per class, and the
 // cut (one workgroup: the k-th smallest score by rank counting in LDS, a prefix sum of the keep flags, the copy).
+// The class rule, the partition, the arg-max's order and the cut are row_merge.h's, shared with mask_nms.hip.
 #include <math.h>
 
 #include "cp_common.h"
+#include "row_merge.h"
 
 #pragma clang fp contract(off)
 
@@ -33,50 +35,15 @@ namespace {
 constexpr int kMaxRows = 4096;
 constexpr int kMaxSegs = 64;
 constexpr int kMaxClasses = 64;
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / CP_WAVE;
+constexpr int kThreads = row_merge::kThreads;
+constexpr int kCutRows = kMaxRows / kThreads;                             // slots of the cut per thread
 
-// LDS writes of some lanes become visible to the other lanes of the same wave (which runs in lock-step: no barrier)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using row_merge::score_key;
+using row_merge::wave_max_key;
+using row_merge::wave_sync;
 
 // bytes of LDS a segment of `cap` rows needs: columns 0-4, the pre-decay score, the flag
 __host__ __device__ inline size_t nms_lds_bytes(int cap) { return (size_t)cap * (6 * sizeof(float) + 1); }
-
-// A score and its position in one word whose order is the arg-max's: a higher score wins, then the lower position
-// (-0 and +0 are equal scores).  Every key of a position is above 0, the key of "nothing".
-__device__ __forceinline__ unsigned long long score_key(float s, int pos) {
-  if (s == 0.f) s = 0.f;
-  unsigned u = __float_as_uint(s);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 32) | (0xffffffffu - (unsigned)pos);
-}
-
-// the largest key of the 64 lanes, in every lane: DPP row shifts and row broadcasts (a lane without a source keeps its
-// own key, and max is idempotent), the result read from lane 63.  All 64 lanes are active where this is called.
-template <int CTRL, int ROWS>
-__device__ __forceinline__ unsigned long long max_key_dpp(unsigned long long k) {
-  const int lo = (int)(unsigned)k, hi = (int)(unsigned)(k >> 32);
-  const unsigned olo = (unsigned)__builtin_amdgcn_update_dpp(lo, lo, CTRL, ROWS, 0xf, false);
-  const unsigned ohi = (unsigned)__builtin_amdgcn_update_dpp(hi, hi, CTRL, ROWS, 0xf, false);
-  const unsigned long long o = ((unsigned long long)ohi << 32) | olo;
-  return o > k ? o : k;
-}
-
-__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long k) {
-  k = max_key_dpp<0x111, 0xf>(k);                                         // row_shr:1
-  k = max_key_dpp<0x112, 0xf>(k);                                         // row_shr:2
-  k = max_key_dpp<0x114, 0xf>(k);                                         // row_shr:4
-  k = max_key_dpp<0x118, 0xf>(k);                                         // row_shr:8: lane 15 of a row holds the row's
-  k = max_key_dpp<0x142, 0xa>(k);                                         // row_bcast:15 into rows 1, 3: lanes 31, 63 two rows'
-  k = max_key_dpp<0x143, 0xc>(k);                                         // row_bcast:31 into rows 2, 3: lane 63 all four
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)k, 63);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(k >> 32), 63);
-  return ((unsigned long long)hi << 32) | lo;
-}
 
 struct Decay {                // the segment in LDS and the parameters
   float *x1, *y1, *x2, *y2, *sc, *old;
@@ -264,43 +231,15 @@ struct MergeArgs {
   int M, ncols, C, max_per_image;
 };
 
-// the class of a row as `cls == j` of the numpy split sees it: -1 when no j of [0, C) equals it
-__device__ __forceinline__ int class_of(float c, int C) {
-  const int ci = (c >= 0.f && c < (float)C) ? (int)c : -1;
-  return ci >= 0 && (float)ci == c ? ci : -1;
-}
-
 __global__ __launch_bounds__(kThreads) void merge_partition_kernel(MergeArgs a) {
   __shared__ signed char s_cls[kMaxRows];
   __shared__ unsigned short s_rank[kMaxRows];                             // position of a row within its class
   __shared__ int s_cnt[kMaxClasses];
   __shared__ int s_start[kMaxClasses];
-  const int t = threadIdx.x, lane = t & (CP_WAVE - 1), wave = t / CP_WAVE;
-  for (int r = t; r < a.M; r += kThreads) s_cls[r] = (signed char)class_of(a.rows[(long long)r * a.ncols + 5], a.C);
-  __syncthreads();
-  const unsigned long long below = (1ull << lane) - 1ull;
-  for (int j = wave; j < a.C; j += kWaves) {                              // one wave per class in turn: the order is fixed
-    int run = 0;
-    for (int r0 = 0; r0 < a.M; r0 += CP_WAVE) {
-      const int r = r0 + lane;
-      const bool mine = r < a.M && s_cls[r] == j;
-      const unsigned long long m = __ballot(mine);
-      if (mine) s_rank[r] = (unsigned short)(run + __popcll(m & below));
-      run += __popcll(m);
-    }
-    if (lane == 0) s_cnt[j] = run;
-  }
-  __syncthreads();
-  if (t == 0) {
-    int acc = 0;
-    for (int j = 0; j < a.C; ++j) {
-      s_start[j] = acc;
-      a.seg_start[j] = acc;
-      a.seg_len[j] = s_cnt[j];
-      acc += s_cnt[j];
-    }
-  }
-  __syncthreads();
+  const int t = threadIdx.x;
+  for (int r = t; r < a.M; r += kThreads)
+    s_cls[r] = (signed char)row_merge::class_of(a.rows[(long long)r * a.ncols + 5], a.C);
+  row_merge::class_partition(s_cls, s_rank, s_cnt, s_start, a.M, a.C, a.seg_start, a.seg_len);
   const long long total = (long long)a.M * a.ncols;
   for (long long e = t; e < total; e += kThreads) {
     const int r = (int)(e / a.ncols), c = (int)(e - (long long)r * a.ncols);
@@ -309,70 +248,15 @@ __global__ __launch_bounds__(kThreads) void merge_partition_kernel(MergeArgs a) 
   }
 }
 
+// the slots are the rows of `sorted`, stale ones included: each holds a row, its score is the row's own
 __global__ __launch_bounds__(kThreads) void merge_cut_kernel(MergeArgs a) {
-  __shared__ __align__(16) float s_score[kMaxRows];
-  __shared__ int s_excl[kMaxRows + 1];                                    // kept rows before row r
-  __shared__ int s_wave[kWaves];
-  __shared__ float s_thresh;
-  const int t = threadIdx.x, lane = t & (CP_WAVE - 1), wave = t / CP_WAVE;
+  __shared__ row_merge::CutLds<kCutRows> s_cut;
   int total = a.seg_start[a.C - 1] + a.seg_len[a.C - 1];
   total = total < 0 ? 0 : (total > a.M ? a.M : total);
-  for (int r = t; r < total; r += kThreads) s_score[r] = a.sorted[(long long)r * a.ncols + 4];
-  if (t == 0) { s_thresh = -__builtin_inff(); s_excl[0] = 0; }
-  __syncthreads();
-  const bool cut = total > a.max_per_image;
-  if (cut) {                                                              // np.partition(scores, kth)[kth]
-    const int kth = total - a.max_per_image;
-    for (int r = t; r < total; r += kThreads) {
-      const float v = s_score[r];
-      int lt = 0, le = 0;
-      for (int j = 0; j < total; ++j) {                                   // every lane reads the same address
-        const float w = s_score[j];
-        lt += w < v ? 1 : 0;
-        le += w <= v ? 1 : 0;
-      }
-      if (lt <= kth && kth < le) s_thresh = v;                            // ties write the same value
-    }
-  }
-  __syncthreads();
-  const float thresh = s_thresh;
-  // keep flags of rows 4t .. 4t + 3 and their prefix sum over the workgroup
-  int keep[4], mine = 0;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int r = 4 * t + q;
-    keep[q] = r < total && (!cut || s_score[r] >= thresh) ? 1 : 0;
-    mine += keep[q];
-  }
-  int incl = mine;
-#pragma unroll
-  for (int o = 1; o < CP_WAVE; o <<= 1) {
-    const int up = __shfl_up(incl, o, CP_WAVE);
-    if (lane >= o) incl += up;
-  }
-  if (lane == CP_WAVE - 1) s_wave[wave] = incl;
-  __syncthreads();
-  int before = incl - mine;
-  for (int w = 0; w < wave; ++w) before += s_wave[w];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    before += keep[q];
-    s_excl[4 * t + q + 1] = before;
-  }
-  __syncthreads();
-  if (t == 0) a.counts[0] = s_excl[total];
-  if (t < a.C) {
-    int s0 = a.seg_start[t], s1 = s0 + a.seg_len[t];
-    s0 = s0 < 0 ? 0 : (s0 > total ? total : s0);
-    s1 = s1 < s0 ? s0 : (s1 > total ? total : s1);
-    a.counts[1 + t] = s_excl[s1] - s_excl[s0];
-  }
-  const long long n = (long long)total * a.ncols;
-  for (long long e = t; e < n; e += kThreads) {
-    const int r = (int)(e / a.ncols), c = (int)(e - (long long)r * a.ncols);
-    const int d = s_excl[r];
-    if (s_excl[r + 1] != d) a.out[(long long)d * a.ncols + c] = a.sorted[e];
-  }
+  row_merge::cut_rows(
+      s_cut, total, row_merge::EverySlot(), [&](int r) { return a.sorted[(long long)r * a.ncols + 4]; },
+      [&](int r) { return a.sorted + (long long)r * a.ncols; }, a.seg_start, a.seg_len, a.C, a.max_per_image, a.ncols,
+      a.out, a.counts);
 }
 
 size_t sorted_bytes(int S, int K, int ncols) { return cp_align_up((size_t)S * K * ncols * sizeof(float), 16); }

@@ -245,7 +245,7 @@ def test_polygon_overlaps_match_pil(name):
     assert np.array_equal(again[0], area) and np.array_equal(again[1], inter)
 
 
-def _merge_device(rows, C, H, W, par):
+def _merge_device(rows, C, H, W, par, nms=1):
     """cp_merge_detections_mask on host rows [S, K, ncols]: (table out[:counts[0]], counts)."""
     lib = _C.lib()
     S, K, ncols = rows.shape
@@ -254,7 +254,7 @@ def _merge_device(rows, C, H, W, par):
     out = torch.from_numpy(np.full((S * K, ncols), SENTINEL, np.uint32).view(np.float32)).cuda()
     counts = torch.full((1 + C,), -7, dtype=torch.int32, device="cuda")
     ws = _C.workspace(lib.cp_merge_detections_mask_workspace_bytes(S, K, ncols, C, H, W), dev.device)
-    _C.check(lib.cp_merge_detections_mask(_C.ptr(dev), S, K, ncols, C, int(mpi), 1, float(sigma), float(Nt), float(thr),
+    _C.check(lib.cp_merge_detections_mask(_C.ptr(dev), S, K, ncols, C, int(mpi), int(nms), float(sigma), float(Nt), float(thr),
                                           int(method), H, W, _C.ptr(out), _C.ptr(counts), _C.ptr(ws), ws.numel(),
                                           _C.stream()), "cp_merge_detections_mask")
     assert _same_bits(dev.cpu().numpy(), np.ascontiguousarray(rows))      # the input is not written
