@@ -129,6 +129,8 @@ _SIGNATURES = {
     "cp_rle_encode": (c_int32, [_P, _P, c_int32, c_int32, c_int32, _P, _P, c_int64, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "cp_rle_decode_workspace_bytes": (c_size_t, [c_int32, c_int64]),
     "cp_rle_decode": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t, _P]),
+    "cp_png_deflate_workspace_bytes": (c_size_t, [c_int32] * 4),
+    "cp_png_deflate": (c_int32, [_P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "cp_boundary_overlaps_workspace_bytes": (c_size_t, [c_int32] * 5),
     "cp_boundary_overlaps": (c_int32, [_P, c_int32, _P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, _P, _P, _P, _P,
                                        _P, c_size_t, _P]),

@@ -340,12 +340,20 @@ class CityscapesWriterMixin(object):
                                     gt_ids, **extra)
             if not write_files:
                 continue
-            masks = masks_dev.cpu().numpy()
+            device_png = getattr(self.opt, "device_png", False)
+            masks = None if device_png else masks_dev.cpu().numpy()
+            names = []
             with open(os.path.join(save_dir, base.replace(".png", ".txt")), "w") as text_file:
                 for count, (k, conf) in enumerate(zip(kept, confs)):
                     name = base.replace(".png", "_" + str(count) + ".png")
                     text_file.write("masks/" + name + " " + str(self.label_to_id[params[k][2]]) + " " + conf + "\n")
-                    Image.fromarray(masks[k]).save(os.path.join(masks_dir, name))
+                    if device_png:
+                        names.append(os.path.join(masks_dir, name))
+                    else:
+                        Image.fromarray(masks[k]).save(os.path.join(masks_dir, name))
+            if names:                                                     # --device_png: compressed on the device
+                from ...utils import png
+                png.write(names, planes=masks_dev if len(kept) == len(params) else masks_dev[kept])
 
 
 class ClassWriterMixin(object):
@@ -556,12 +564,20 @@ class ClassWriterMixin(object):
                 continue
             write_dir = os.path.join(save_dir, os.path.basename(os.path.dirname(file_name))) if self.per_city else save_dir
             os.makedirs(write_dir, exist_ok=True)
-            masks = masks_dev.cpu().numpy()
+            device_png = getattr(self.opt, "device_png", False)
+            masks = None if device_png else masks_dev.cpu().numpy()
+            names = []
             with open(os.path.join(write_dir, base.replace(".png", ".txt")), "w") as text_file:
                 for count, (k, lab, conf) in enumerate(zip(by_line, labels, confs)):
                     name = base.replace(".png", "_" + str(count) + ".png")
                     text_file.write(name + " " + str(lab) + " " + conf + "\n")
-                    Image.fromarray(masks[k]).save(os.path.join(write_dir, name))
+                    if device_png:
+                        names.append(os.path.join(write_dir, name))
+                    else:
+                        Image.fromarray(masks[k]).save(os.path.join(write_dir, name))
+            if names:                                                     # --device_png: compressed on the device
+                from ...utils import png
+                png.write(names, planes=masks_dev[by_line])
 
     def run_eval(self, results, save_dir):
         """kitti_poly.py / IDD.py run_eval: results.json + the per-image mask files their instance-level evaluation

@@ -218,7 +218,22 @@ def id_array(path, image, bits):
     return np.ascontiguousarray(arr.astype(np.uint16 if bits == 16 else np.uint8))
 
 
-def write_id_png(path, image, bits=16):
-    """A 16-bit (mode I;16) or 8-bit (mode L) PNG of an id image: a device or host tensor or an array."""
+def write_id_png(path, image, bits=16, device_png=False):
+    """A 16-bit (mode I;16) or 8-bit (mode L) PNG of an id image: a device or host tensor or an array.  device_png: a
+    device tensor is compressed on the device (utils/png.py) and only the file's bytes come back; the same ValueError
+    for a value that does not fit."""
+    if device_png and isinstance(image, torch.Tensor) and image.is_cuda:
+        from ..utils import png
+        if image.dim() != 2 or image.dtype not in (torch.int32, torch.int16, torch.uint8, torch.int64):
+            raise ValueError("%s: an id image is a 2-D integer array, got %s %s" % (path, tuple(image.shape), image.dtype))
+        if bits not in (8, 16):
+            raise ValueError("an id image has 8 or 16 bits, not %r" % (bits,))
+        if image.dtype == torch.int64 and image.numel():
+            lo, hi = int(image.min()), int(image.max())                   # (int32 below would wrap these around)
+            bad = lo if lo < 0 else hi if hi >= 1 << bits else None
+            if bad is not None:
+                raise ValueError("%s: the value %d does not fit a %d-bit image" % (path, bad, bits))
+        png.write([path], images=image.to(torch.int32), bits=bits)
+        return
     from PIL import Image
     Image.fromarray(id_array(path, image, bits)).save(path, format="PNG")

@@ -216,15 +216,16 @@ def instance_entry(maps, k):
             "polygon": [[int(x), int(y)] for x, y in t["poly"][k]]}
 
 
-def save_ids(maps, out_dir, stem):
+def save_ids(maps, out_dir, stem, device_png=False):
     """--save_ids: <stem>_instanceIds.png (16 bit), <stem>_labelIds.png (8 bit) and <stem>.json (one entry per live
-    instance) in out_dir.  Returns the three paths."""
+    instance) in out_dir; device_png: the two images compressed on the device (utils/png.py).  Returns the three
+    paths."""
     from ..datasets.ground_truth import write_id_png
     os.makedirs(out_dir, exist_ok=True)
     paths = [os.path.join(out_dir, stem + "_instanceIds.png"), os.path.join(out_dir, stem + "_labelIds.png"),
              os.path.join(out_dir, stem + ".json")]
-    write_id_png(paths[0], maps.ids, 16)
-    write_id_png(paths[1], maps.labels, 8)
+    write_id_png(paths[0], maps.ids, 16, device_png=device_png)
+    write_id_png(paths[1], maps.labels, 8, device_png=device_png)
     t = maps.table
     entries = [instance_entry(maps, k) for k in range(t["n"]) if t["live"][k]]
     with open(paths[2], "w") as f:
@@ -233,20 +234,34 @@ def save_ids(maps, out_dir, stem):
     return paths
 
 
-def save_masks(maps, out_dir, stem):
+def save_masks(maps, out_dir, stem, device_png=False):
     """--save_masks: <stem>.txt with one line `masks/<stem>_<k>.png <label id> <confidence>` per live instance and the
     masks as 8-bit PNG files, the Cityscapes result layout (evaluation.instance_level.evaluate_result_dir reads it)
-    for every data set.  Returns the text file's path."""
+    for every data set.  device_png: the masks are compressed on the device within the polygons' bounds, one call for
+    all live slots (utils/png.py), and only the compressed bytes come back.  Returns the text file's path."""
     from PIL import Image
     os.makedirs(os.path.join(out_dir, "masks"), exist_ok=True)
     slots = maps.written()
-    masks = maps.masks.cpu().numpy() if slots else None
+    masks = maps.masks.cpu().numpy() if slots and not device_png else None
     path = os.path.join(out_dir, stem + ".txt")
+    names = []
     with open(path, "w") as f:
         for count, k in enumerate(slots):
             name = "masks/%s_%d.png" % (stem, count)
             f.write("%s %d %s\n" % (name, int(maps.table["label"][k]), maps.conf_text(k)))
-            Image.fromarray(masks[k]).save(os.path.join(out_dir, name))
+            if device_png:
+                names.append(os.path.join(out_dir, name))
+            else:
+                Image.fromarray(masks[k]).save(os.path.join(out_dir, name))
+    if names:
+        from ..utils import png
+        bounds = vertex_bounds_host(maps.table["poly"], MARGIN[maps.family], maps.canvas)
+        n = int(maps.table["n"])
+        if list(slots) == list(range(n)):
+            png.write(names, planes=maps.masks[:n], bounds=bounds)
+        else:
+            sel = torch.as_tensor(slots, dtype=torch.long, device=maps.masks.device)
+            png.write(names, planes=maps.masks.index_select(0, sel), bounds=bounds[slots])
     return path
 
 

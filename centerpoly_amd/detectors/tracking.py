@@ -260,12 +260,12 @@ class InstanceTracker(object):
         return TrackedFrame(ids, track_of_instance, tab, frame, int(multiplier))
 
 
-def save_tracks(maps, tracked, out_dir, stem):
+def save_tracks(maps, tracked, out_dir, stem, device_png=False):
     """--track --save_ids: `<stem>_tracks.json` (per live instance: track id, label, score, box, is_new; under
     --track_motion also centroid [x, y] in pixels and velocity [vx, vy] in pixels per frame of its track) and
     `<stem>_trackIds.png` (16 bit, label * multiplier + track_id) in out_dir.  The PNG cannot hold a track id that
     reaches the multiplier: a ValueError that names the frame; the JSON has no such limit and is written first.
-    Returns the two paths."""
+    device_png: the PNG is compressed on the device (utils/png.py).  Returns the two paths."""
     import json
     import os
 
@@ -288,7 +288,7 @@ def save_tracks(maps, tracked, out_dir, stem):
     if worst >= tracked.multiplier or max([e["label_id"] for e in entries], default=0) * tracked.multiplier + worst > 65535:
         raise ValueError("%s (frame %d of its sequence): track id %d does not fit label * %d + track_id in 16 bits; "
                          "%s holds the tracks" % (stem, tracked.frame, worst, tracked.multiplier, paths[0]))
-    write_id_png(paths[1], tracked.ids, 16)
+    write_id_png(paths[1], tracked.ids, 16, device_png=device_png)
     return paths
 
 

@@ -120,6 +120,10 @@ class opts(object):
                             "run_eval scores the masks on the GPU (Cityscapes instance-level AP); empty: files only")
         p.add_argument("--no_mask_files", action="store_true",
                        help="with --gt_dir: score in memory and skip the PNG and text output")
+        p.add_argument("--device_png", action="store_true",
+                       help="compress every mask and id PNG (run_eval's mask files, --save_masks, --save_ids, "
+                            "_trackIds.png) on the GPU and read back only the files' bytes: one fixed-Huffman block of "
+                            "run-length matches, larger files than PIL's with the same pixels; off: PIL on the host")
         p.add_argument("--save_ids", action="store_true",
                        help="demo.py / test.py: per image <stem>_instanceIds.png (16 bit), <stem>_labelIds.png (8 bit) "
                             "and <stem>.json (the live instances) under <save_dir>/instances/, from the detections "

@@ -56,6 +56,7 @@ def demo(opt):
         from centerpoly_amd.detectors import tracking
         seq = tracking.SequenceTracker(opt.track_iou, opt.track_max_age, getattr(opt, "track_motion", False))
     save_rle, mots_files = getattr(opt, "save_rle", False), None
+    device_png = getattr(opt, "device_png", False)
     for name in names:
         ret = detector.run(name)
         print("".join("{} {:.3f}s |".format(stat, ret[stat]) for stat in time_stats)
@@ -71,11 +72,11 @@ def demo(opt):
                         mots_files = tracking.MotsWriter(inst_dir, getattr(opt, "mots_classes", None))
                     mots_files.add(key, maps, ret["tracked"], stem)
                 if opt.save_ids:
-                    tracking.save_tracks(maps, ret["tracked"], inst_dir, stem)
+                    tracking.save_tracks(maps, ret["tracked"], inst_dir, stem, device_png=device_png)
             if opt.save_ids:
-                instances.save_ids(maps, inst_dir, stem)
+                instances.save_ids(maps, inst_dir, stem, device_png=device_png)
             if opt.save_masks:
-                instances.save_masks(maps, inst_dir, stem)
+                instances.save_masks(maps, inst_dir, stem, device_png=device_png)
             if save_rle:
                 instances.save_rle(maps, inst_dir, stem)
         if getattr(opt, "save_panoptic", False):

@@ -59,7 +59,7 @@ extern "C" {
                               cp_boundary_overlaps(_workspace_bytes), cp_polygon_overlaps(_workspace_bytes),
                               cp_merge_detections_mask(_workspace_bytes), cp_map_pairs, cp_track_associate, cp_track_update,
                               cp_rle_encode(_workspace_bytes), cp_rle_decode(_workspace_bytes), cp_map_pairs_shifted,
-                              cp_track_predict, cp_track_kinematics(_workspace_bytes) */
+                              cp_track_predict, cp_track_kinematics(_workspace_bytes), cp_png_deflate(_workspace_bytes) */
 
 enum {
   CP_OK = 0,
@@ -878,6 +878,49 @@ int cp_rle_encode(const uint8_t* planes, const uint8_t* index, int32_t n, int32_
 size_t cp_rle_decode_workspace_bytes(int32_t n, int64_t total_counts);
 int cp_rle_decode(const uint32_t* counts, const int32_t* table, int32_t n, int32_t H, int32_t W, int32_t value,
                   uint8_t* planes, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------ device PNG stream (utils/png.py) --
+ * The zlib stream of a grey PNG image, 8 or 16 bit, compressed on the device so that only compressed bytes go to the
+ * host, which frames them (signature, IHDR, one IDAT, IEND, CRC-32s).  Not in the reference tree: the format is zlib's
+ * (RFC 1950, RFC 1951) with every choice fixed below, pinned by the literal host statement tests/golden/png_host.py;
+ * zlib and PIL decode it.
+ *
+ * Filtered stream.  D = bits / 8 bytes per pixel, 16-bit pixels big-endian.  S is H rows of one filter byte 0 (filter
+ * "None") followed by W * D pixel bytes; its length is L = H * (1 + W * D).
+ * Tokens, chosen greedily from i = 0: r = the number of consecutive positions j = i, i + 1, ... with j >= D and
+ * S[j] == S[j - D], capped at 258 and at L - i.  r >= 3: a match (length r, distance D), advance by r; otherwise the
+ * literal S[i], advance by 1.  (Equivalently, in a maximal interval [a, b) of positions equal to their D-predecessor
+ * the chunks of 258 from a are matches, the remainder (b - a) mod 258 is one match if >= 3 and else 1 or 2 literals,
+ * and every other position is a literal.  Runs cross row ends; the filter byte is an ordinary byte of S.)
+ * zlib stream, bits packed LSB first, Huffman codes MSB first: bytes 0x78 0x01; BFINAL = 1, BTYPE = 01 (one
+ * fixed-Huffman block); the tokens; end-of-block (symbol 256); zero bits to a byte; Adler-32 of S, big-endian.
+ * Literal/length codes: symbols 0-143 8 bits from 0x30, 144-255 9 bits from 0x190, 256-279 7 bits from 0, 280-287 8
+ * bits from 0xC0.  Length symbol 257 + k: k 0-7 bases 3..10, no extra bits; 8-11 bases 11, 13, 15, 17, 1 bit; 12-15
+ * bases 19, 23, 27, 31, 2 bits; 16-19 bases 35, 43, 51, 59, 3 bits; 20-23 bases 67, 83, 99, 115, 4 bits; 24-27 bases
+ * 131, 163, 195, 227, 5 bits; k = 28 is 258, no extra bits.  The extra bits follow the length code, LSB first; the
+ * distance is the 5-bit code D - 1 with no extra bits.
+ *
+ * cp_png_deflate: the zlib streams of n images in one call, seven launches and a fill whatever n is.
+ *   planes_u8   DEVICE uint8 [n][H][W], bits = 8: the bytes as they are         -- exactly one of the two is non-NULL --
+ *   images_i32  DEVICE int32 [n][H][W], bits 8 or 16: the low `bits` bits of every value (the caller refuses an image
+ *               whose range in `table` does not fit)
+ *   bounds      DEVICE int32 [n][4] inclusive x0, y0, x1, y1, or NULL, as in cp_rle_encode: the caller promises that
+ *               image k is zero outside its box (W, H, -1, -1: empty); nothing outside it is read
+ *   out         DEVICE bytes [cap_bytes] out, 4-byte aligned: the streams back to back (NULL only with cap_bytes == 0)
+ *   table       DEVICE int32 [n][4] out = byte offset, byte length of the stream, minimum, maximum of the values
+ *   head        DEVICE int32 [4] out = bytes needed in total, overflow flag, 0, 0
+ * When the total exceeds cap_bytes the flag is 1 and no stream is written (out is zero); table and head are complete
+ * all the same, so a second call at head[0] succeeds.  Nothing is ever written at or beyond out + cap_bytes.  Sizes
+ * beyond int32 saturate.  n > 128, H or W > 16384, n * L >= 2^31: CP_EUNSUPPORTED; both or neither input, planes_u8
+ * with bits 16, bits not 8 or 16, n < 1, non-positive H or W, a negative capacity, null table, head or (with cap_bytes
+ * > 0) out, misaligned pointers: CP_EINVAL; workspace NULL or shorter than cp_png_deflate_workspace_bytes (40 bytes
+ * per tile of 4096 stream bytes and the per-image records; 16-byte aligned): CP_EWORKSPACE.  All checks come before
+ * any device work.  Whole words leave as vector stores; a word shared by two tiles or two streams is merged with an
+ * integer atomic OR into the zeroed output, which commutes: the same bytes on every run. */
+size_t cp_png_deflate_workspace_bytes(int32_t n, int32_t H, int32_t W, int32_t bits);
+int cp_png_deflate(const uint8_t* planes_u8, const int32_t* images_i32, int32_t n, int32_t H, int32_t W, int32_t bits,
+                   const int32_t* bounds, uint8_t* out, int64_t cap_bytes, int32_t* table, int32_t* head,
+                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------ boundary evaluation (evaluation/boundary.py) --
  * cp_boundary_overlaps: the pixel counting of Boundary IoU / Boundary AP (Cheng et al., CVPR 2021) for ONE image --

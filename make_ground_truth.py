@@ -13,7 +13,8 @@ gives `..._gtFine_instanceids.png`, the file `test.py --gt_dir` scores against),
 `<stem>_labelIds.png` for Cityscapes (`...TrainIds.png` with --id_type trainIds).  --no_instance leaves the instance
 image out.  The colour images, the panoptic output and the domain-adaptation subsets of createLabels.py are not made.
 The JSON is parsed and the list of polygons to draw is made in --num_workers DataLoader workers ahead of the device;
-the same number of threads compresses the PNGs behind it."""
+the same number of threads compresses the PNGs behind it.  With --device_png the painted image is compressed on the
+GPU before it leaves the device (centerpoly_amd/utils/png.py) and the threads only write the files' bytes."""
 import argparse
 import json
 import os
@@ -38,6 +39,8 @@ def parse_args(argv=None):
     p.add_argument("--no_instance", action="store_true", help="do not write the instance image")
     p.add_argument("--labels", action="store_true", help="also write the label image")
     p.add_argument("--num_workers", type=int, default=4)
+    p.add_argument("--device_png", action="store_true",
+                   help="compress the PNGs on the GPU (larger files, same pixels); the threads then only write bytes")
     p.add_argument("--gpu", type=int, default=0)
     opt = p.parse_args(argv)
     from centerpoly_amd.datasets import ground_truth
@@ -137,6 +140,11 @@ def output_dir(opt, path):
     return os.path.normpath(os.path.join(opt.out_dir, rel))
 
 
+def write_bytes(path, data):
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 def run(opt):
     """Writes the images; returns the list of files written, in frame order."""
     from concurrent.futures import ThreadPoolExecutor
@@ -144,6 +152,7 @@ def run(opt):
     import torch
 
     from centerpoly_amd.datasets import eval_images, ground_truth
+    from centerpoly_amd.utils import png
     names = frame_list(opt.dataset, opt.gt_dir)
     for path in names:
         check_size_fields(path)
@@ -164,7 +173,11 @@ def run(opt):
                 for (kind, which, bits), (polygons, values, background) in zip(kinds, item["lists"]):
                     image = ground_truth.paint(polygons, values, background, item["canvas"], dev)
                     out = os.path.join(out_dir, files[which])
-                    pending.append(pool.submit(ground_truth.write_id_png, out, image.cpu().numpy(), bits))
+                    if getattr(opt, "device_png", False):
+                        data = png.encode(images=image, bits=bits, names=[out])[0]
+                        pending.append(pool.submit(write_bytes, out, data))
+                    else:
+                        pending.append(pool.submit(ground_truth.write_id_png, out, image.cpu().numpy(), bits))
                     written.append(out)
                 while len(pending) > 4 * max(1, opt.num_workers):   # a bounded queue of images that wait for a thread
                     pending.pop(0).result()

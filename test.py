@@ -75,6 +75,7 @@ def run_test(opt, evaluate=True):
         return per_image
 
     save_ids, save_masks = getattr(opt, "save_ids", False), getattr(opt, "save_masks", False)
+    device_png = getattr(opt, "device_png", False)
     save_rle, segm = getattr(opt, "save_rle", False), []
     inst_dir = os.path.join(opt.save_dir, "instances")
 
@@ -87,9 +88,9 @@ def run_test(opt, evaluate=True):
         from centerpoly_amd.detectors import instances
         stem = instances.image_stem(file_name)
         if save_ids:
-            instances.save_ids(maps, inst_dir, stem)
+            instances.save_ids(maps, inst_dir, stem, device_png=device_png)
         if save_masks:
-            instances.save_masks(maps, inst_dir, stem)
+            instances.save_masks(maps, inst_dir, stem, device_png=device_png)
 
     def save_rle_instances(item, file_name, maps, rows):
         """--save_rle: <stem>_rle.json, and the image's entries of results_segm.json (the class and the score are the
@@ -180,7 +181,7 @@ def run_test(opt, evaluate=True):
                 if seq is not None:                                        # step per image, in the loader's order
                     key, tracked = seq.step(file_name, maps)
                     if save_ids:
-                        tracking.save_tracks(maps, tracked, inst_dir, instances_stem(file_name))
+                        tracking.save_tracks(maps, tracked, inst_dir, instances_stem(file_name), device_png=device_png)
                     if mots_files is not None:
                         mots_files.add(key, maps, tracked, instances_stem(file_name))
                     if mots is not None:
