@@ -69,6 +69,27 @@ enum {
   CP_EHIP = -4          /* a HIP runtime call or kernel launch failed */
 };
 
+/* ------------------------------------------------------------ memory contract --
+ * For every entry point, unless its own comment says otherwise (tests/test_memory_contract.py holds each of them to it):
+ *   * A `workspace` is scratch.  Its contents on entry are ARBITRARY -- stale data of an earlier call, of another
+ *     entry or of nothing at all -- and whatever a call needs zeroed in it the call zeroes itself.  Its contents
+ *     after the call mean nothing to the caller.  The exceptions are named where they occur: the CP_DCN_*_PREPARED
+ *     modes and `prepared` of cp_dcn_v2_forward_fused read the weights an earlier call left at its head,
+ *     cp_dcn_v2_forward_slices leaves its partial sums in it for the caller, and cp_poly_iou_order_backward reads the
+ *     object count its forward left.
+ *   * A workspace of exactly cp_*_workspace_bytes(...) bytes is enough: no byte before it or from that length on is
+ *     read or written, whatever rounding an allocator would have added.
+ *   * An output is OVERWRITTEN, every element of the extent its comment gives and from any previous contents, so it
+ *     may be handed over uninitialised.  The outputs that are ADDED to instead say so: grad_weight / grad_bias of
+ *     the DCN and convolution backward entries, cp_channel_sum_accumulate, grad_feat of cp_gather_l1_backward and
+ *     cp_poly_iou_order_backward, conf and bad of cp_pixel_confusion, stat / iou / bad of cp_panoptic_match; and
+ *     pred_add_out of cp_poly_iou_order_forward is written in part only (the caller zero-fills it).
+ *   * Where a call reports a count or a capacity (counts[0] rows of the mask merge, n_out instances, cap_counts /
+ *     cap_bytes of cp_rle_encode, cap_bytes of cp_png_deflate, segments of cp_soft_nms_device), nothing is written
+ *     at or beyond the capacity, and elements between a reported count and the capacity hold what the entry's
+ *     comment says (dead slots) or are not specified; nothing outside the output's stated extent is ever touched.
+ *   * Inputs are never written (in-place forms, such as cp_sigmoid_focal_forward's heat map, are named as such). */
+
 /* representation of the polygon head (src/lib/opts.py `--rep`) */
 enum { CP_REP_CARTESIAN = 0, CP_REP_POLAR = 1, CP_REP_POLAR_FIXED = 2 };
 
@@ -1452,8 +1473,10 @@ int cp_dense_l1_backward(const float* pred, const float* target, const float* ma
  * early-terminating traversal).  flags: bit0 = IoU term, bit1 = order term.
  *   iou_loss_out[0]   = 1 - sum(iou) / (sum(mask) + 1e-6)          (bit0)
  *   order_loss_out[0] = sum(hinge) / (10*sum(mask) + 1e-4)         (bit1)
- *   pred_add_out [B,M,2N] (bit1): the +2*3.14 edits, to feed cp_gather_l1_*.
- * backward scatter-ADDS into grad_feat (caller zero-fills).
+ *   pred_add_out [B,M,2N] (bit1): the +2*3.14 edits, to feed cp_gather_l1_*.  Only the angle slots (odd) of the
+ *   masked objects are written -- the caller zero-fills it; the two losses are overwritten.
+ * backward scatter-ADDS into grad_feat (caller zero-fills).  The forward takes a workspace of arbitrary contents and
+ * leaves the object count in it; the backward READS that count, so it is handed the forward's workspace, unchanged.
  */
 size_t cp_poly_iou_order_workspace_bytes(int32_t B, int32_t M, int32_t N);
 int cp_poly_iou_order_forward(const float* feat, const int64_t* ind, const uint8_t* mask,

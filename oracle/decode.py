@@ -36,7 +36,10 @@ def topk(scores, K):
     topk_ys = (topk_inds / W).int().float()
     topk_xs = (topk_inds % W).int().float()
     topk_score, topk_ind = _topk_stable(topk_scores.view(B, -1), K)
-    topk_clses = (topk_ind / K).int()
+    # every class hands on min(K, H * W) candidates (the reference's torch.topk(K) raises on a map of fewer than K
+    # pixels; the device entry takes one): the class of a winner is its place divided by that count, which is K
+    # wherever the reference runs
+    topk_clses = (topk_ind / topk_scores.shape[-1]).int()
     g = lambda t: torch.gather(t.view(B, -1), 1, topk_ind)
     return topk_score, g(topk_inds), topk_clses, g(topk_ys), g(topk_xs)
 

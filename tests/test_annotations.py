@@ -27,9 +27,13 @@ if ROOT not in sys.path:
 PATH_ROOT = "/ROOT"                                             # what the recorded file names start with
 
 
+def load_fixture():
+    return np.load(os.path.join(HERE, "golden", "annotations.npz"), allow_pickle=False)
+
+
 @pytest.fixture(scope="module")
 def z():
-    return np.load(os.path.join(HERE, "golden", "annotations.npz"), allow_pickle=False)
+    return load_fixture()
 
 
 _built = {}

@@ -29,9 +29,13 @@ if ROOT not in sys.path:
 NAMES = sorted(gc.CASES)
 
 
+def load_fixture():
+    return np.load(os.path.join(HERE, "golden", "ground_truth.npz"), allow_pickle=False)
+
+
 @pytest.fixture(scope="module")
 def z():
-    return np.load(os.path.join(HERE, "golden", "ground_truth.npz"), allow_pickle=False)
+    return load_fixture()
 
 
 def sequence_of(z, name):

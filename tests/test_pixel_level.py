@@ -19,9 +19,10 @@ CS = pl.CITYSCAPES
 
 
 def run_kernel(pred, ids, inst_ids, pred_label=IDENTITY, proto=CS, L=None, group=None, conf=None, inst_fill=0,
-               pred_offset=0, ids_offset=0, null_tables=False):
+               pred_offset=0, ids_offset=0, null_tables=False, bad=None):
     """The kernel on host arrays pred uint8 [H, W] and ids uint16 [H, W], uploaded `pred_offset` bytes / `ids_offset`
-    elements into their buffers: (conf int64 [L, L], inst int64 [G, 3], bad int64 [2]) as the device leaves them."""
+    elements into their buffers: (conf int64 [L, L], inst int64 [G, 3], bad int64 [2]) as the device leaves them; conf
+    and bad start from the given tables (zeros when None)."""
     import torch
     dev = torch.device("cuda")
     H, W = pred.shape
@@ -35,7 +36,7 @@ def run_kernel(pred, ids, inst_ids, pred_label=IDENTITY, proto=CS, L=None, group
     conf_dev = torch.from_numpy(np.zeros(L * L, np.int64) if conf is None else conf.reshape(-1).copy()).to(dev)
     inst_dev = torch.full((max(3 * G, 1),), inst_fill, dtype=torch.int32, device=dev)
     ids_dev = torch.tensor([int(v) for v in inst_ids] or [0], dtype=torch.int32).to(dev)
-    bad_dev = torch.zeros(2, dtype=torch.int32, device=dev)
+    bad_dev = torch.from_numpy(np.zeros(2, np.int32) if bad is None else np.array(bad, np.int32)).to(dev)
     lib = _C.lib()
     nbytes = lib.cp_pixel_confusion_workspace_bytes(G)
     ws = _C.workspace(nbytes, dev)

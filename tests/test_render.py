@@ -362,7 +362,12 @@ def _device_overlay(image, rows, thresh, names, palette, white=False, show_txt=T
     prm = _C.OverlayParams(alpha, r, t, int(white), int(show_txt), int(show_polygons))
     prm.outline_colour[:] = outline
     nbytes = L.cp_render_overlay_workspace_bytes(H, W)
-    ws = torch.full((nbytes,), 0xAB, dtype=torch.uint8, device=dev)       # stale on purpose: the call clears it
+    # stale on purpose: the call clears it.  Taken from _C.workspace so that tests/test_memory_contract.py can hand it an
+    # exact-size, guard-banded payload; such a payload already holds a uniform non-zero fill, which is kept -- anything
+    # else (the allocator's own memory, or the zero fill) is replaced by 0xAB as before
+    ws = _C.workspace(nbytes, dev)
+    if int(ws[0]) == 0 or not bool((ws == ws[0]).all()):
+        ws.fill_(0xAB)
     _C.check(L.cp_render_overlay(_C.ptr(d_img), H, W, _C.ptr(d_rows), R, N, _C.ptr(n), _C.ptr(src), _C.ptr(poly),
                                  _C.ptr(d_pal), C, _C.ptr(d_codes), 16, _C.ptr(d_atlas), 96, ctypes.byref(prm),
                                  _C.ptr(d_out), _C.ptr(ws), nbytes, _C.stream()), "cp_render_overlay")

@@ -214,17 +214,16 @@ def _gt_frame(t, centres, labels, multiplier):
     return gt
 
 
-@pytest.fixture(scope="module", params=["cityscapes", "kitti_poly"])
-def sequence(request):
+def build_sequence(name):
     """Six frames through instance_maps and the tracker (max_age 3 for Cityscapes, 0 for KITTI): per frame the maps,
     the TrackedFrame and the tracker's mem / state, all on the host, and the ground truth."""
     import torch
     from centerpoly_amd.detectors import tracking
     from centerpoly_amd.detectors.instances import instance_maps
-    ds = tia._dataset(request.param)
+    ds = tia._dataset(name)
     C_of = {name: ds.class_name.index(name) - 1 for name in ("car", "person")}
     labels = [int(ds.label_to_id[c]) for c in ("car", "car", "car", "person")]
-    max_age = 3 if request.param == "cityscapes" else 0
+    max_age = 3 if name == "cityscapes" else 0
     tr = tracking.InstanceTracker((W, H), 0.3, max_age)
     frames = []
     for t in range(6):
@@ -235,8 +234,13 @@ def sequence(request):
                        "ids": tracked.ids.cpu().numpy(), "index": maps.index.cpu().numpy(),
                        "track_of_instance": tracked.track_of_instance.cpu().numpy(),
                        "gt": _gt_frame(t, centres, labels, maps.multiplier)})
-    return {"name": request.param, "ds": ds, "tracker": tr, "frames": frames, "max_age": max_age,
+    return {"name": name, "ds": ds, "tracker": tr, "frames": frames, "max_age": max_age,
             "multiplier": frames[0]["maps"].multiplier}
+
+
+@pytest.fixture(scope="module", params=["cityscapes", "kitti_poly"])
+def sequence(request):
+    return build_sequence(request.param)
 
 
 def test_whole_steps_against_the_host_statement(sequence):
